@@ -24,7 +24,11 @@ numerator = sum over layers and relations of E_r = 800M edges/step.
   rank, data-parallel over N ranks).
 
 value = all ranks' edges / max-over-ranks wall time of exactly ``--steps`` steps, bracketed by a
-barrier + device synchronise, with NO per-kernel events inside.  A second, separately timed run
+barrier + device synchronise, with NO per-kernel events inside; ``ms_per_step`` is that wall time
+per step.  A plain run does only this: set up, warm up, time the steps, write the last timed
+step's results with ``--dump-outputs DIR``, print the line.  Everything below runs with ``--full``
+only (without it the line's ``roofline``, ``projection``, ``cpu_baseline``, ``dist`` are null and
+``kernels`` is empty).  ``--full``: a second, separately timed run
 of ``--timer-steps`` steps records HIP events around every kernel (on the stream it is launched
 on) for ``roofline`` — the dominant HBM kernel, the K1 forward gather over the largest source
 table: algorithmic bytes per launch / average launch time, ``traffic`` from the committed PMC
@@ -121,9 +125,18 @@ def parse(argv=None):
                         "launches, read-backs) and stage its batches, instead of the sync-free "
                         "LinkSampler")
     p.add_argument("--scale", type=float, default=1.0, help="shrink the config (debug only)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run what the headline does not need: the "
+                        "per-kernel-event run (roofline, projection, kernels, dist) and the CPU "
+                        "baseline")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step computed (loss, every parameter after "
+                        "the step and its gradient, a fixed row sample of the output embeddings "
+                        "where the step returns them) as DIR/<name>.npy, float32")
     p.add_argument("--timer-steps", type=int, default=5,
-                   help="steps of the separate per-kernel-event run (0: none)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+                   help="--full: steps of the separate per-kernel-event run (0: none)")
+    p.add_argument("--no-cpu-baseline", action="store_true",
+                   help="--full without the CPU baseline")
     p.add_argument("--cpu-threads", type=int, default=None,
                    help="default: the box's allotted CPUs (OMP_NUM_THREADS / affinity)")
     p.add_argument("--cpu-sample-scale", type=float, default=None,
@@ -574,6 +587,7 @@ def _run_full_batch(args, dev, world, rank, local, sharded, impl):
     gen = torch.Generator(device=dev).manual_seed(synth.NEG_SEED + rank)
     rels = relations_of(cfg)
     t_setup = time.perf_counter()
+    last = {} if args.dump_outputs else None    # --dump-outputs: the last step's embeddings
     if not sharded:
         g = synth.make_graph(cfg, device=dev, device_gen=True)   # the graph the shards hold
         pos = g.edge_index_dict[synth.ENGAGES]
@@ -602,6 +616,8 @@ def _run_full_batch(args, dev, world, rank, local, sharded, impl):
                 pre.rowptr.record_stream(main)
                 pre.users.record_stream(main)
             out = model(g.x_dict, g.edge_index_dict)
+            if last is not None:
+                last["out"] = out
             if presort["on"]:
                 torch.cuda.current_stream(dev).wait_stream(side)
             return ops.edge_bce_loss(out["user"], out["post"], pos, neg, pw, neg_order="user",
@@ -674,9 +690,17 @@ def _run_full_batch(args, dev, world, rank, local, sharded, impl):
     setup_s = time.perf_counter() - t_setup
     elapsed, loss = clock.time(step, args.steps)             # the headline: no events inside
     value = edges_step * args.steps / elapsed                 # edges_step is the global count
+    # the reference's train() returns the global loss: sum the per-rank shares
+    loss_t = loss.detach().to(torch.float64).reshape(1).clone()
+    if sharded:
+        dist.all_reduce(loss_t)
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, loss_t, model, (last or {}).get("out"))
+    last = None
     # per-kernel HIP events: a separate run, so the headline carries none of their cost
     kern, timer_ms, dist_rec = {}, None, None
-    if not args.profile_steps and args.timer_steps > 0 and (sharded or not on_cpu):
+    if (args.full and not args.profile_steps and args.timer_steps > 0
+            and (sharded or not on_cpu)):
         # one stream: a kernel's events around its launch then time that kernel alone (the
         # negatives grouping, overlapped with the forward in the timed steps, runs in the loss).
         # N > 1: every collective's issue and its consumer's wait marked too (parallel.
@@ -701,10 +725,6 @@ def _run_full_batch(args, dev, world, rank, local, sharded, impl):
         timer_ms = t_el / args.timer_steps * 1e3
         if trace is not None:
             dist_rec = _dist_summary(trace, kern, args.timer_steps, timer_ms, dev)
-    # the reference's train() returns the global loss: sum the per-rank shares
-    loss_t = loss.detach().to(torch.float64).reshape(1).clone()
-    if sharded:
-        dist.all_reduce(loss_t)
     if rank != 0:
         return None
     roof = _roofline(kern, cfg, world)
@@ -712,7 +732,7 @@ def _run_full_batch(args, dev, world, rank, local, sharded, impl):
         roof["one_pass"] = _one_pass_k1(g, cfg, roof)
     proj = _projection(kern, cfg.name)
     cpu = None
-    if not args.no_cpu_baseline and world == 1 and not on_cpu and not sharded:
+    if args.full and not args.no_cpu_baseline and world == 1 and not on_cpu and not sharded:
         if set(et for et, _ in rels) == {synth.ENGAGES, synth.REV_ENGAGES}:
             cpu = cpu_baseline_shard(cfg, g, rels, args.cpu_threads, args.cpu_shard,
                                      steps=args.cpu_steps)
@@ -749,6 +769,41 @@ def _run_full_batch(args, dev, world, rank, local, sharded, impl):
         "loss": float(loss_t),
         "setup_s": round(setup_s, 1),
     }
+
+
+DUMP_MAX_BYTES = 64 * 2 ** 20   # --dump-outputs writes at most this much in all
+DUMP_SAMPLE_ROWS = 16384        # rows kept of each output embedding table
+DUMP_SEED = 20240607
+
+
+def _dump_outputs(path, loss, model, out):
+    """``--dump-outputs``: what a caller of the timed step holds after the last timed step, as
+    float32 ``<name>.npy`` files under ``path``: the step's ``loss`` (float64), every parameter after its
+    Adam update (``param.<name>``) and the gradient that update consumed (``grad.<name>``), and,
+    where the step returns the model's embeddings (N = 1 full batch), ``DUMP_SAMPLE_ROWS`` rows
+    of each table (``out.<type>``; the same seeded row sample on every run, all rows of a
+    smaller table).  The graph, the weights and the negatives are seeded, so two builds run with
+    the same arguments write comparable files."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": loss.detach().reshape(1)}
+    for name, p in model.named_parameters():
+        arrays[f"param.{name}"] = p.detach()
+        if p.grad is not None:
+            arrays[f"grad.{name}"] = p.grad.detach()
+    for t, v in sorted((out or {}).items()):
+        v = v.detach()
+        if v.shape[0] > DUMP_SAMPLE_ROWS:
+            rows = torch.randperm(v.shape[0], generator=torch.Generator().manual_seed(DUMP_SEED))
+            v = v.index_select(0, rows[:DUMP_SAMPLE_ROWS].sort().values.to(v.device))
+        arrays[f"out.{t}"] = v
+    total = 0
+    for name, v in arrays.items():
+        a = v.to(torch.float64 if name == "loss" else torch.float32).cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f"--dump-outputs: more than {DUMP_MAX_BYTES} bytes at {name}")
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _dist_summary(trace, kern, steps, step_ms, dev):
@@ -1268,8 +1323,10 @@ def _run_minibatch(args, dev, world, rank, local, sharded, impl):
         dist.all_reduce(edges)
     edges = float(edges)
     phases = ph.summary(args.steps) if ph else None
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, loss, model, None)
     kern = {}
-    if not args.profile_steps and args.timer_steps > 0:
+    if args.full and not args.profile_steps and args.timer_steps > 0:
         # per-kernel events need the eager launches: the timer steps run the same kernels
         # without the graph (on each batch's real sizes, not the static capacities)
         timer = ops.KernelTimer()
@@ -1281,7 +1338,7 @@ def _run_minibatch(args, dev, world, rank, local, sharded, impl):
         return None
     kern = _pool_shapes(kern)
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         lb, ev = nxt[0] if nxt[0] is not None else (None, None)
         if lb is None:                           # a LinkBatch of the next batch's edges
             lb, ev = sample(state["b"], prep=False, eager=True)

@@ -28,7 +28,7 @@ def _line(tmp_path, argv):
 def test_bench_gpus_n_spawns_n_ranks(tmp_path, monkeypatch, n):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         monkeypatch.delenv(k, raising=False)
-    line = _line(tmp_path, ["--gpus", str(n), "--timer-steps", "1"] + SMALL)
+    line = _line(tmp_path, ["--gpus", str(n), "--full", "--timer-steps", "1"] + SMALL)
     assert line["n_gpus"] == n
     assert line["scaling"] == "strong"             # cfg's own graph split n ways
     assert line["steps"] == 2 and line["value"] > 0
@@ -62,6 +62,44 @@ def test_bench_weak_label(tmp_path, monkeypatch):
     line = _line(tmp_path, ["--gpus", "2", "--weak"] + SMALL)
     assert line["n_gpus"] == 2 and line["scaling"] == "weak"
     assert line["config"]["edges_per_step"] == 2 * 2 * 2 * 10_000
+
+
+def test_bench_plain_run_times_and_dumps_only(tmp_path, monkeypatch):
+    """Without ``--full`` the run is the timed steps alone (no per-kernel-event run, so no
+    ``dist`` record and no kernel table, even with ``--timer-steps`` given), and
+    ``--dump-outputs`` writes the last timed step's loss, parameters and gradients as float
+    arrays; a second run with the same arguments starts from the same inputs."""
+    import numpy as np
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        monkeypatch.delenv(k, raising=False)
+    dumps = []
+    for d in ("a", "b"):
+        line = _line(tmp_path, ["--gpus", "2", "--timer-steps", "1", "--dump-outputs",
+                                str(tmp_path / d)] + SMALL)
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert abs(line["value"] - 2 * 2 * 10_000 / (line["ms_per_step"] * 1e-3)) \
+            <= 1e-3 * line["value"]
+        assert line["dist"] is None and line["kernels"] == {} and line["roofline"] is None
+        assert line["cpu_baseline"] is None and line["kernel_timer"]["steps"] == 0
+        files = {f.name: np.load(f) for f in (tmp_path / d).iterdir()}
+        assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+        assert sum(a.nbytes for a in files.values()) <= 64 * 2 ** 20
+        assert files["loss.npy"].shape == (1,) and float(files["loss.npy"][0]) == line["loss"]
+        params = [n for n in files if n.startswith("param.")]
+        # 2 layers x 2 relations x (lin_l.weight, lin_l.bias, lin_r.weight), each with its grad
+        assert len(params) == 12 and all("grad." + n[len("param."):] in files for n in params)
+        assert all(np.isfinite(a).all() for a in files.values())
+        dumps.append(files)
+    assert dumps[0].keys() == dumps[1].keys()
+    for n, a in dumps[0].items():
+        if n.startswith("param."):
+            # float32 summation order differs between runs (threads, gloo); Adam moves a
+            # parameter by at most ~lr = 1e-3 per step, whichever way a near-zero gradient's
+            # rounding noise points
+            np.testing.assert_allclose(dumps[1][n], a, rtol=0, atol=2 * 1e-3 * 3)
+        else:
+            np.testing.assert_allclose(dumps[1][n], a, rtol=1e-4,
+                                       atol=1e-5 * (float(np.abs(a).max()) or 1.0))
 
 
 def test_bench_refuses_world_size_mismatch(monkeypatch):
