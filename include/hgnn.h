@@ -283,6 +283,15 @@ int hgnn_adam_multi(int32_t n_tensors, float* const* params, const float* const*
                     float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel,
                     float* step, uint32_t* done, double lr, double beta1, double beta2, double eps,
                     double weight_decay, hgnn_stream_t stream);
+/* A 64-bit checksum of the bit patterns of n_elems fp32 words (one streaming pass):
+ *   *d_out = sum_i bits(x[i]) * (0x9E3779B97F4A7C15 + 2 i)  (mod 2^64)
+ * Integer sums only, so the value does not depend on the order of the blocks; any single flipped
+ * bit and any exchange of two unequal words change it.  d_out: one device uint64 (8-byte aligned;
+ * zeroed by the call on the same stream).  A caller that keeps a result computed from a static
+ * table (e.g. hgnn_gather_mean_fwd of the model's inputs, run once) can keep this value beside it
+ * and compare it later to detect a table rewritten in place. */
+int hgnn_table_fingerprint(const float* x, int64_t n_elems, uint64_t* d_out,
+                           hgnn_stream_t stream);
 int hgnn_linear_bwd(int32_t n_seg, const float* const* xs, const int32_t* ks, int64_t n_rows,
                     const float* w, int32_t h, const float* dout, const float* out,
                     float* const* dxs, float* dw, float* db, void* ws, size_t ws_bytes,

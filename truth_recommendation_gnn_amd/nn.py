@@ -166,7 +166,9 @@ class _LayoutModel(torch.nn.Module):
                 rels.append((et[0], relation_csr(ei, x_dict[et[0]].shape[0],
                                                  x_dict[dst].shape[0])))
             root = any(convs[name].lin_r is not None for name, _, _ in msgs)
-            groups.append(ops.DstGroup(dst, tuple(rels), root, relu))
+            # the one layer of these models reads the model's inputs: static unless they train
+            static = tuple(not x_dict[et[0]].requires_grad for _, et, _ in msgs)
+            groups.append(ops.DstGroup(dst, tuple(rels), root, relu, static=static))
         weights = _fused_weights_layer(convs, list(self.layout.values()), x_dict)
         return ops.hetero_layer(ops.LayerSpec(types, tuple(groups)), dict(x_dict), weights)
 
@@ -242,7 +244,7 @@ class HeteroSAGE(torch.nn.Module):
     def forward(self, x_dict, edge_index_dict):
         h = dict(x_dict)
         dsts = sorted({et[2] for et, _ in self.relations})
-        for convs in self.layers:
+        for li, convs in enumerate(self.layers):
             types = tuple(sorted(h))
             groups, msgs_g = [], []
             for dst in dsts:
@@ -251,7 +253,13 @@ class HeteroSAGE(torch.nn.Module):
                                                   h[dst].shape[0])) for _, et, _ in msgs)
                 pre = tuple(ops.use_pre_projection(h[et[0]], h[dst], self.hidden_dim, True)
                             for _, et, _ in msgs)
-                groups.append(ops.DstGroup(dst, rels, True, True, pre))
+                # layer 1 reads the model's inputs, the same tables every step (the reference
+                # builds x_dict once): their aggregates are static unless the table trains.
+                # Deeper layers read layer outputs — never static, also under no_grad, where
+                # every intermediate has requires_grad == False too.
+                static = tuple(li == 0 and not p and not h[et[0]].requires_grad
+                               for p, (_, et, _) in zip(pre, msgs))
+                groups.append(ops.DstGroup(dst, rels, True, True, pre, static=static))
                 msgs_g.append(msgs)
             weights = _fused_weights_layer(convs, msgs_g, h)
             out = ops.hetero_layer(ops.LayerSpec(types, tuple(groups)), h, weights)

@@ -17,6 +17,7 @@ from __future__ import annotations
 import contextlib
 import dataclasses
 import os
+import weakref
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -142,14 +143,163 @@ def _gather_blocked(x, passes, row_w, edge_w, out, accumulate, name, nbytes, cby
                 p.n_chunks, p.chunk, N.ptr(slab), N.ptr(out), s), "hgnn_gather_reduce_scaled")
 
 
+# ----------------------------------------------------------------------------- static aggregates
+# The mean of a model INPUT table over a relation is the same every step (the reference builds
+# x_dict once, train_gnn.py:87-88,118-119, and passes it unchanged to every epoch's forward and
+# to evaluation, :254,391,424).  A caller that knows a table is such an input says so
+# (``gather_mean(..., static=True)``; nn.HeteroSAGE / the layout models at their first layer) and
+# the aggregate is computed once and kept on the RelationCSR — at cfg4 a 200M-edge gather per
+# direction (~205 GB of random row reads per step) for 5.1 GB held.  Nothing here guesses: an
+# unflagged call always runs its kernel.
+#
+# HGNN_STATIC_AGG: "1" (default) keep them; "0" never; "check" keep them and verify the table's
+# checksum (hgnn_table_fingerprint, one streaming pass over the table) on every hit.
+STATIC_AGG = os.environ.get("HGNN_STATIC_AGG", "1")
+_STATIC_HOLDERS: "weakref.WeakSet" = weakref.WeakSet()   # RelationCSRs holding an entry
+
+
+class StaleAggregateError(RuntimeError):
+    """HGNN_STATIC_AGG=check: a table's memory changed under a kept aggregate."""
+
+
+class _StaticEntry:
+    """One kept aggregate: the table it was computed from (weakly), what identifies the table's
+    contents (pointer, shape, strides, version counter, the blocking the gather ran with), the
+    aggregate, and under ``check`` the table's fingerprint (a device int64)."""
+    __slots__ = ("ref", "key", "value", "fp", "event", "stream", "fin", "__weakref__")
+
+    def __init__(self, x, key, value, fp):
+        self.ref, self.key, self.value, self.fp = weakref.ref(x), key, value, fp
+        self.event = self.stream = self.fin = None
+        if value.is_cuda:
+            # a hit on another stream waits for the fill (same stream: in order already)
+            self.stream = torch.cuda.current_stream(value.device)
+            self.event = torch.cuda.Event()
+            self.event.record(self.stream)
+
+
+def _static_key(x: torch.Tensor, blocks: int):
+    return (x.data_ptr(), tuple(x.shape), tuple(x.stride()), x._version, int(blocks))
+
+
+def table_fingerprint(x: torch.Tensor) -> torch.Tensor:
+    """``hgnn_table_fingerprint`` of a contiguous fp32 tensor: a device int64 holding the 64-bit
+    checksum's bits (no host sync)."""
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        raise TypeError("table_fingerprint: a contiguous float32 tensor")
+    dev = N.require_device(x)
+    out = torch.empty(1, dtype=torch.int64, device=dev)
+    with _timed("table_fingerprint", 4 * x.numel()):
+        N.check(N.lib().hgnn_table_fingerprint(N.ptr(x), x.numel(), N.ptr(out),
+                                               N.stream_ptr(dev)), "hgnn_table_fingerprint")
+    return out
+
+
+def _static_enabled(x: torch.Tensor) -> bool:
+    if STATIC_AGG == "0":
+        return False
+    # a recorded graph must hold its own kernels: nothing is kept from, or served into, a capture
+    return not (x.is_cuda and torch.cuda.is_current_stream_capturing())
+
+
+def _static_drop(csr_ref, entry_ref) -> None:
+    """The table died: drop its entry (if it is still the relation's)."""
+    csr, entry = csr_ref(), entry_ref()
+    if csr is not None and entry is not None and csr.__dict__.get("_static_agg") is entry:
+        del csr.__dict__["_static_agg"]
+        _STATIC_HOLDERS.discard(csr)
+
+
+def _static_lookup(x: torch.Tensor, csr: RelationCSR, blocks: int, name: Optional[str],
+                   fingerprint=table_fingerprint) -> Optional[torch.Tensor]:
+    """The kept aggregate of ``x`` over ``csr``, or None: a hit needs the same live tensor
+    object at the same pointer, shape, strides and version."""
+    entry = csr.__dict__.get("_static_agg")
+    if entry is None:
+        return None
+    if entry.ref() is not x or entry.key != _static_key(x, blocks):
+        return None
+    if STATIC_AGG == "check":
+        if entry.fp is None:          # kept before the check was switched on: recompute
+            return None
+        if int(fingerprint(x)) != int(entry.fp):   # (a host sync per hit)
+            what = name or f"{csr.n_src}->{csr.n_dst} rows"
+            raise StaleAggregateError(
+                f"static aggregate of relation {what} ({csr.num_edges} edges): the source "
+                "table's memory changed without a version bump (a kernel wrote it through a raw "
+                "pointer?) — call ops.clear_static_aggregates() after such a write")
+    if entry.event is not None:
+        cur = torch.cuda.current_stream(entry.value.device)
+        if cur != entry.stream:
+            cur.wait_event(entry.event)
+    return entry.value
+
+
+def _static_store(x: torch.Tensor, csr: RelationCSR, blocks: int, value: torch.Tensor,
+                  fingerprint=table_fingerprint) -> None:
+    """Keep ``value`` as the aggregate of ``x`` over ``csr`` (replacing the relation's entry)."""
+    fp = fingerprint(x) if STATIC_AGG == "check" else None
+    old = csr.__dict__.get("_static_agg")
+    if old is not None and old.fin is not None:
+        old.fin.detach()      # (a table changed in place every step leaves no finalizers behind)
+    entry = _StaticEntry(x, _static_key(x, blocks), value, fp)
+    csr.__dict__["_static_agg"] = entry
+    _STATIC_HOLDERS.add(csr)
+    entry.fin = weakref.finalize(x, _static_drop, weakref.ref(csr), weakref.ref(entry))
+
+
+def _static_aggregate(x: torch.Tensor, csr: RelationCSR, blocks: int, name: Optional[str],
+                      compute, fingerprint=table_fingerprint) -> torch.Tensor:
+    """``compute()`` once per (table, relation): the kept result on a hit, else computed and kept
+    (``compute`` / ``fingerprint`` are parameters so the keying is testable without a GPU)."""
+    if not _static_enabled(x):
+        return compute()
+    kept = _static_lookup(x, csr, blocks, name, fingerprint)
+    if kept is None:
+        kept = compute()
+        _static_store(x, csr, blocks, kept, fingerprint)
+    return kept
+
+
+def clear_static_aggregates() -> None:
+    """Drop every kept static aggregate.  Whoever rewrites an input table through a raw pointer
+    (a native kernel writing into it or into a view of it: no version bump) must call this."""
+    for csr in list(_STATIC_HOLDERS):
+        csr.__dict__.pop("_static_agg", None)
+    _STATIC_HOLDERS.clear()
+
+
+def static_aggregate_count() -> int:
+    """Number of kept static aggregates (live relations holding one)."""
+    return sum(1 for csr in list(_STATIC_HOLDERS) if "_static_agg" in csr.__dict__)
+
+
 def gather_mean(x_src: torch.Tensor, csr: RelationCSR,
-                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                out: Optional[torch.Tensor] = None, static: bool = False,
+                name: Optional[str] = None) -> torch.Tensor:
     """K1: ``aggr[i] = mean_{(j->i)} x_src[j]`` (0 for an empty row); added into ``out`` when
-    given."""
+    given.
+
+    ``static=True``: the caller declares ``x_src`` a static model input (never a layer output,
+    never a sampled block's buffer).  The aggregate is then computed once by this same call and
+    kept on ``csr`` for as long as ``x_src`` lives unchanged: the key holds the tensor weakly with
+    its ``data_ptr()``, shape, strides and ``_version``, so an in-place torch op, a new tensor or
+    the table's death all miss.  The returned tensor is shared between calls and MUST NOT be
+    written.  A write to the table that bypasses torch (a native kernel through a raw pointer)
+    bumps no version: whoever does that must call :func:`clear_static_aggregates`
+    (``HGNN_STATIC_AGG=check`` verifies a checksum of the table on every hit and raises
+    :class:`StaleAggregateError`, naming the relation by ``name``).  ``HGNN_STATIC_AGG=0`` turns
+    the keeping off."""
+    if static and out is not None:
+        raise ValueError("gather_mean: a static aggregate is never accumulated into (out=)")
+    given = x_src
     x_src = _check_f32(x_src, "gather_mean")
     dev = N.require_device(x_src, csr.fwd.rowptr)
     if x_src.shape[0] != csr.n_src:
         raise ValueError(f"x_src has {x_src.shape[0]} rows, relation expects {csr.n_src}")
+    if static and x_src is given and not x_src.requires_grad:
+        B = gather_blocks(x_src, csr.num_edges) if csr.num_edges else 1
+        return _static_aggregate(x_src, csr, B, name, lambda: gather_mean(x_src, csr))
     d = int(x_src.shape[1])
     acc = out is not None
     if out is None:
@@ -195,9 +345,26 @@ def _gather_multi(jobs, mean: bool, accumulate: bool, edge_ws=None, acc_limit=No
         N.ptr_array([o for _, _, o in jobs]), N.stream_ptr(dev)), "hgnn_gather_reduce_multi")
 
 
-def gather_mean_many(pairs: Sequence[Tuple[torch.Tensor, RelationCSR]]) -> List[torch.Tensor]:
+def gather_mean_many(pairs: Sequence[Tuple[torch.Tensor, RelationCSR]],
+                     static: Sequence[bool] = (), names: Sequence[Optional[str]] = ()
+                     ) -> List[torch.Tensor]:
     """``gather_mean(x, csr)`` of every pair — one launch for all of them when they qualify
-    (sampled blocks: short rows, one pass each; ``_multi_ok``), else one call each."""
+    (sampled blocks: short rows, one pass each; ``_multi_ok``), else one call each.
+    ``static[i]``: pair i's table is a static model input (see :func:`gather_mean`); such pairs
+    go through the kept aggregates one by one and only the rest are launched here."""
+    if any(static) and STATIC_AGG != "0":
+        res: List[Optional[torch.Tensor]] = [None] * len(pairs)
+        rest = []
+        for i, (x, csr) in enumerate(pairs):
+            if i < len(static) and static[i]:
+                res[i] = gather_mean(x, csr, static=True,
+                                     name=names[i] if i < len(names) else None)
+            else:
+                rest.append(i)
+        if rest:
+            for i, o in zip(rest, gather_mean_many([pairs[i] for i in rest])):
+                res[i] = o
+        return res
     jobs = []
     for x, csr in pairs:
         x = _check_f32(x, "gather_mean")
@@ -731,6 +898,16 @@ class DstGroup:
     # the root segment is the whole input ``root_src`` instead (a block whose relations gather
     # from the global tables: its destinations' own rows come as a separate input)
     root_src: Optional[str] = None
+    # per relation: the source table is a static model INPUT (first layer, no gradient, not
+    # pre-projected), declared by the caller — its mean aggregate is kept across calls
+    # (gather_mean's ``static``).  Never set for a deeper layer or a sampled block.
+    static: Tuple[bool, ...] = ()
+
+
+def _is_static(g: DstGroup, i: int) -> bool:
+    """Relation i of the group reads a table its caller declared static (never a pre-projected
+    relation: that one gathers the projected rows, which change with the weights)."""
+    return bool(i < len(g.static) and g.static[i] and not (i < len(g.pre) and g.pre[i]))
 
 
 def _root_type(g: DstGroup) -> str:
@@ -845,8 +1022,10 @@ class _HeteroLayer(torch.autograd.Function):
         if lanes.side is None and not any(any(g.pre) for g in spec.groups):
             # every relation's K1 of the layer in one launch (sampled blocks; gather_mean_many
             # falls back to one launch each where they do not qualify)
-            many = iter(gather_mean_many([(xs[src], csr) for g in spec.groups
-                                          for src, csr in g.rels]))
+            many = iter(gather_mean_many(
+                [(xs[src], csr) for g in spec.groups for src, csr in g.rels],
+                static=[_is_static(g, i) for g in spec.groups for i in range(len(g.rels))],
+                names=[f"{src}->{g.dst}" for g in spec.groups for src, _ in g.rels]))
         if many is not None:
             # and every destination type's K3 in one native call (the split path's column blocks
             # one launch for both types, hgnn_linear_fwd_multi)
@@ -869,13 +1048,14 @@ class _HeteroLayer(torch.autograd.Function):
                     # one [N_dst, h] input) and added in the destination update's epilogue
                     cols = _group_columns(g, xs)
                     add, aggrs = None, []
-                    for (src, csr), pre, (o, k) in zip(g.rels, g.pre, cols):
+                    for i, ((src, csr), pre, (o, k)) in enumerate(zip(g.rels, g.pre, cols)):
                         if pre:
                             P = linear_fwd([xs[src]], w[:, o:o + k].contiguous(), None, False)
                             add = gather_mean(P, csr, out=add)
                             del P
                         else:
-                            aggrs.append(gather_mean(xs[src], csr))
+                            aggrs.append(gather_mean(xs[src], csr, static=_is_static(g, i),
+                                                     name=f"{src}->{g.dst}"))
                     segs = aggrs + ([_root(g, xs)] if g.root else [])
                     mk = relu_mask_for(_root(g, xs).shape[0], int(w.shape[0]), g.relu, dev,
                                        sum(int(t.shape[1]) for t in segs))
@@ -884,7 +1064,9 @@ class _HeteroLayer(torch.autograd.Function):
                                    mask_out=mk)
                     del add
                 else:
-                    aggrs = [gather_mean(xs[src], csr) for src, csr in g.rels]
+                    aggrs = [gather_mean(xs[src], csr, static=_is_static(g, i),
+                                         name=f"{src}->{g.dst}")
+                             for i, (src, csr) in enumerate(g.rels)]
                     segs = aggrs + ([_root(g, xs)] if g.root else [])
                     mk = relu_mask_for(segs[0].shape[0], int(w.shape[0]), g.relu, dev,
                                        sum(int(t.shape[1]) for t in segs))
@@ -1139,6 +1321,11 @@ def _pre_group_backward(g: DstGroup, xs, aggrs, w, dout, y, need_x, need_w, need
 def hetero_layer(spec: LayerSpec, x_dict: Dict[str, torch.Tensor],
                  weights: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]]
                  ) -> Dict[str, torch.Tensor]:
+    for g in spec.groups:
+        if any(g.static) and (g.n_root is not None or g.root_src is not None):
+            # a block's tables are buffers native kernels refill through raw pointers (no
+            # version bump): an aggregate kept from them would be replayed stale
+            raise ValueError("hetero_layer: a sampled block's relations are never static")
     flat: List[Optional[torch.Tensor]] = [x_dict[t] for t in spec.types]
     for w, b in weights:
         flat.extend([w, b])
