@@ -112,6 +112,30 @@ int hgnn_plan_fill(const int32_t* rowptr, int64_t n_rows, int32_t chunk, int32_t
 /* inv_deg[i] = 1/(rowptr[i+1]-rowptr[i]) or 0 for an empty row. */
 int hgnn_inv_degree(const int32_t* rowptr, int64_t n_rows, float* inv_deg, hgnn_stream_t stream);
 
+/* ---- hot-row flags -------------------------------------------------------------------------
+ * col_hot[k] = col[k] | 0x80000000 when source row col[k] is among the n_hot most referenced of
+ * the n_src rows, else col[k]: same order and length as col, read by the gathers below in its
+ * place.  A row's reference count is deg_rowptr[i+1] - deg_rowptr[i] (the rowptr of the opposite
+ * grouping, n_src + 1 entries); equal counts go to the lower id, so the set is deterministic.
+ * *d_hot_edges (device int64, zeroed by the call) receives the number of edges whose row is
+ * flagged; the caller keeps hot_edges / n_edges (the hot rows' share) with col_hot.  The flag
+ * takes bit 31, so n_src above 2^31 is refused (HGNN_E_ARG).  Static per graph: built once. */
+size_t hgnn_hot_cols_ws_bytes(int64_t n_src);
+int hgnn_hot_cols(const int32_t* deg_rowptr, int64_t n_src, const int32_t* col, int64_t n_edges,
+                  int64_t n_hot, int32_t* col_hot, int64_t* d_hot_edges, void* ws,
+                  size_t ws_bytes, hgnn_stream_t stream);
+/* The rule by which a gather with a col_hot takes the two-policy loads (1) or its old path (0):
+ * a hot row is read with the default cache policy, every other row with nt loads, which keep it
+ * out of L2 and the Infinity Cache, so the caches hold the Zipf head instead of a tail of rows
+ * referenced once or twice.  On when the gathered table has at least 256 MiB (it outgrows the
+ * Infinity Cache), a col_hot is given and the hot rows' share of the edges is at least 0.5
+ * (cfg4's K1 / K2 over the 1M-row post table gain 6.5 - 7 % with 32768 - 131072 hot rows, 48 -
+ * 65 % of the edges; with 8192 rows, 35 %, nothing; with 4096, 29 %, they lose 5 %).
+ * Environment: HGNN_HOT_ROWS=0 off, HGNN_HOT_ROWS=force on for any table that comes with a
+ * col_hot (tests).  No GPU needed.  The loss's scoring pass has no such path: measured, it lost
+ * at every number of hot rows. */
+int32_t hgnn_hot_rows_policy(int64_t table_bytes, int32_t has_col_hot, float hot_share);
+
 /* ---- K1/K2: segmented gather-reduce over a CSR ----------------------------------------------
  *   out[i,:] (+)= s_i * sum_{p in [rowptr[i],rowptr[i+1])} w_p * x[col[p],:]
  * with w_p = (edge_w ? edge_w[p] : 1) * (col_w ? col_w[col[p]] : 1), s_i = 1/deg_i under
@@ -122,6 +146,18 @@ int hgnn_gather_reduce(const float* x, int64_t n_x, int32_t d, const int32_t* ro
                        const float* col_w, int32_t flags, const int32_t* heavy_rows,
                        const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
                        int32_t chunk, float* slab, float* out, hgnn_stream_t stream);
+/* hgnn_gather_reduce with a col_hot of the same grouping (hgnn_hot_cols, nullable) and its hot
+ * share: where hgnn_hot_rows_policy(n_x * d * 4, col_hot != NULL, hot_share) says so, a separate
+ * instantiation of the kernel reads col_hot and loads cold rows nt; otherwise exactly
+ * hgnn_gather_reduce.  The edge order is the same, so the sums are bitwise the same either way.
+ * acc_limit > 0 (with HGNN_ACCUMULATE): only rows below it accumulate, as in
+ * hgnn_gather_reduce_multi (here heavy rows included). */
+int hgnn_gather_reduce_hot(const float* x, int64_t n_x, int32_t d, const int32_t* rowptr,
+                           const int32_t* col, int64_t n_rows, const float* edge_w,
+                           const float* col_w, int32_t flags, const int32_t* heavy_rows,
+                           const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
+                           int32_t chunk, float* slab, float* out, int64_t acc_limit,
+                           const int32_t* col_hot, float hot_share, hgnn_stream_t stream);
 
 /* K1 forward: aggr = mean_{(j->i)} x_src[j]  — PyG propagate(aggr='mean') inside SAGEConv:
  * x_src.index_select(0, src) + scatter(..., dst, reduce='mean'), train_gnn.py:177-198. */

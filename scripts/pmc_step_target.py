@@ -76,15 +76,15 @@ def grids(csr, side):
 gb = ops.gather_bytes
 roles = {
     # (kernel-name fragment, grid threads) -> role, algorithmic bytes per launch
-    "gather_fwd[post<-user]": {"kernel": "k_gather<32, 1, 4, 4, false, false>", "grid": grids(eng, "fwd"),
+    "gather_fwd[post<-user]": {"kernel": "k_gather<32, 1, 4, 4, false, false,", "grid": grids(eng, "fwd"),
                                "alg_bytes": gb(E, P, d, False), "per_step": 2},
-    "gather_fwd[user<-post]": {"kernel": "k_gather<32, 1, 4, 4, false, false>", "grid": grid(rev.fwd),
+    "gather_fwd[user<-post]": {"kernel": "k_gather<32, 1, 4, 4, false, false,", "grid": grid(rev.fwd),
                                "alg_bytes": gb(E, U, d, False), "per_step": 2},
-    "gather_bwd[post<-user]": {"kernel": "k_gather<32, 1, 4, 4, true, false>", "grid": grids(rev, "bwd"),
+    "gather_bwd[post<-user]": {"kernel": "k_gather<32, 1, 4, 4, true, false,", "grid": grids(rev, "bwd"),
                                "alg_bytes": gb(E, P, d, True), "per_step": 1},
-    "gather_bwd[user<-post]": {"kernel": "k_gather<32, 1, 4, 4, true, false>", "grid": grid(eng.bwd),
+    "gather_bwd[user<-post]": {"kernel": "k_gather<32, 1, 4, 4, true, false,", "grid": grid(eng.bwd),
                                "alg_bytes": gb(E, U, d, True), "per_step": 1},
-    "score_gather[post<-user]": {"kernel": "k_gather<32, 1, 4, 4, false, true>", "grid": grid(eng.fwd),
+    "score_gather[post<-user]": {"kernel": "k_gather<32, 1, 4, 4, false, true,", "grid": grid(eng.fwd),
                                  "alg_bytes": gb(2 * E, P, d, False) + 4 * (P + 1) + 4 * P * d,
                                  "per_step": 1},
     "edge_score": {"kernel": "k_edge_score", "grid": None,

@@ -38,6 +38,12 @@ _SIGS = {
     "hgnn_inv_degree": (_c_i32, [_p, _c_i64, _p, _p]),
     "hgnn_gather_reduce": (_c_i32, [_p, _c_i64, _c_i32, _p, _p, _c_i64, _p, _p, _c_i32, _p, _p,
                                     _c_i64, _c_i64, _c_i32, _p, _p, _p]),
+    "hgnn_hot_cols_ws_bytes": (_c_sz, [_c_i64]),
+    "hgnn_hot_cols": (_c_i32, [_p, _c_i64, _p, _c_i64, _c_i64, _p, _p, _p, _c_sz, _p]),
+    "hgnn_hot_rows_policy": (_c_i32, [_c_i64, _c_i32, ctypes.c_float]),
+    "hgnn_gather_reduce_hot": (_c_i32, [_p, _c_i64, _c_i32, _p, _p, _c_i64, _p, _p, _c_i32, _p,
+                                        _p, _c_i64, _c_i64, _c_i32, _p, _p, _c_i64, _p,
+                                        ctypes.c_float, _p]),
     "hgnn_gather_reduce_multi": (_c_i32, [_c_i32, _p, _p, _c_i32, _p, _p, _p, _p, _c_i32, _p,
                                           _p, _p]),
     "hgnn_gather_reduce_scaled": (_c_i32, [_p, _c_i64, _c_i32, _p, _p, _c_i64, _p, _p, _p,

@@ -1041,3 +1041,133 @@ int hgnn_inv_degree(const int32_t* rowptr, int64_t n_rows, float* inv_deg,
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------
+// Hot-row flags: col with bit 31 set where the source row is among the relation's H most
+// referenced rows (degree from the opposite grouping's rowptr; ties go to the lower id).  The
+// gathers read it in place of col and pick each row's cache policy from the flag (gather.hip,
+// scoring.hip).  Once per graph, so the selection is one block: a binary search for the H-th
+// largest degree T, then one for the id bound B below which rows of degree exactly T still make
+// the cut — about 50 counting passes over the degrees, ~10 ms at 1M rows.
+// ------------------------------------------------------------------------------------------
+namespace hgnn {
+
+constexpr int kHotThreads = 1024;
+
+// rows i < n with pred(i), the count in every thread of the (single) block
+template <typename F>
+__device__ int32_t block_count(int64_t n, F pred, int32_t* sh) {
+  int32_t c = 0;
+  for (int64_t i = threadIdx.x; i < n; i += kHotThreads) c += pred(i) ? 1 : 0;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
+  __syncthreads();   // sh is free again
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = c;
+  __syncthreads();
+  int32_t t = 0;
+  for (int w = 0; w < kHotThreads / 64; ++w) t += sh[w];
+  return t;
+}
+
+// sel[0] = T, sel[1] = B: row i is hot iff deg_i > T or (deg_i == T and i < B)
+__global__ void __launch_bounds__(kHotThreads) k_hot_select(const int32_t* rowptr, int64_t n,
+                                                            int64_t n_hot, int32_t* sel) {
+  __shared__ int32_t sh[kHotThreads / 64];
+  if (n_hot <= 0 || n <= 0) {   // nothing hot (no degree exceeds or equals INT32_MAX)
+    if (threadIdx.x == 0) {
+      sel[0] = INT32_MAX;
+      sel[1] = 0;
+    }
+    return;
+  }
+  auto deg = [&](int64_t i) { return rowptr[i + 1] - rowptr[i]; };
+  // T = the largest degree that at least n_hot rows reach (n_hot <= n, so T >= 0)
+  int64_t lo = 0, hi = (int64_t)rowptr[n] - rowptr[0];
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo + 1) / 2;
+    const int32_t c = block_count(n, [&](int64_t i) { return deg(i) >= mid; }, sh);
+    if (c >= n_hot) lo = mid; else hi = mid - 1;
+  }
+  const int64_t T = lo;
+  const int64_t need = n_hot - block_count(n, [&](int64_t i) { return deg(i) > T; }, sh);
+  // B = the largest bound with at most `need` rows of degree T below it
+  int64_t blo = 0, bhi = n;
+  while (blo < bhi) {
+    const int64_t mid = blo + (bhi - blo + 1) / 2;
+    const int32_t c = block_count(mid, [&](int64_t i) { return deg(i) == T; }, sh);
+    if (c <= need) blo = mid; else bhi = mid - 1;
+  }
+  if (threadIdx.x == 0) {
+    sel[0] = (int32_t)T;
+    sel[1] = (int32_t)blo;
+  }
+}
+
+// mask[i] = row i is hot; *hot_edges += the edges that reference hot rows (integer sum)
+__global__ void __launch_bounds__(256) k_hot_mark(const int32_t* rowptr, int64_t n,
+                                                  const int32_t* sel, uint8_t* mask,
+                                                  unsigned long long* hot_edges) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int32_t T = sel[0], B = sel[1];
+  long long mine = 0;
+  if (i < n) {
+    const int32_t deg = rowptr[i + 1] - rowptr[i];
+    const bool hot = deg > T || (deg == T && i < B);
+    mask[i] = hot ? 1 : 0;
+    if (hot) mine = deg;
+  }
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) mine += __shfl_xor(mine, m, 64);
+  if ((threadIdx.x & 63) == 0 && mine) atomicAdd(hot_edges, (unsigned long long)mine);
+}
+
+__global__ void __launch_bounds__(256) k_hot_cols(const int32_t* col, int64_t E,
+                                                  const uint8_t* mask, int64_t n,
+                                                  int32_t* col_hot) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= E) return;
+  const int32_t c = col[k];
+  const bool hot = c >= 0 && c < n && mask[c];
+  col_hot[k] = hot ? (int32_t)((uint32_t)c | 0x80000000u) : c;
+}
+
+}  // namespace hgnn
+
+extern "C" {
+
+size_t hgnn_hot_cols_ws_bytes(int64_t n_src) {
+  return align_up((size_t)(n_src < 1 ? 1 : n_src), 256) + 512;
+}
+
+int hgnn_hot_cols(const int32_t* deg_rowptr, int64_t n_src, const int32_t* col, int64_t n_edges,
+                  int64_t n_hot, int32_t* col_hot, int64_t* d_hot_edges, void* ws,
+                  size_t ws_bytes, hgnn_stream_t stream_) {
+  hipStream_t stream = as_stream(stream_);
+  if (n_src < 0 || n_edges < 0 || n_hot < 0)
+    return fail(HGNN_E_ARG, "hot_cols: bad sizes n_src=%lld n_edges=%lld n_hot=%lld",
+                (long long)n_src, (long long)n_edges, (long long)n_hot);
+  // bit 31 of an id carries the flag
+  if (n_src > (int64_t(1) << 31))
+    return fail(HGNN_E_ARG, "hot_cols: n_src=%lld: ids must stay below 2^31", (long long)n_src);
+  if (!d_hot_edges) return fail(HGNN_E_ARG, "hot_cols: d_hot_edges is null");
+  (void)hipMemsetAsync(d_hot_edges, 0, sizeof(int64_t), stream);
+  if (n_edges == 0 || n_src == 0) return check_launch("hot_cols(empty)");
+  if (!deg_rowptr || !col || !col_hot) return fail(HGNN_E_ARG, "hot_cols: null pointer");
+  Workspace w(ws, ws_bytes);
+  uint8_t* mask = w.take<uint8_t>(n_src);
+  int32_t* sel = w.take<int32_t>(2);
+  if (!mask || !sel) return fail(HGNN_E_WS, "hot_cols: workspace too small");
+  if (n_hot > n_src) n_hot = n_src;
+  hipLaunchKernelGGL(k_hot_select, dim3(1), dim3(kHotThreads), 0, stream, deg_rowptr, n_src,
+                     n_hot, sel);
+  if (int rc = check_launch("k_hot_select")) return rc;
+  hipLaunchKernelGGL(k_hot_mark, dim3((unsigned)cdiv(n_src, 256)), dim3(256), 0, stream,
+                     deg_rowptr, n_src, sel, mask,
+                     reinterpret_cast<unsigned long long*>(d_hot_edges));
+  if (int rc = check_launch("k_hot_mark")) return rc;
+  hipLaunchKernelGGL(k_hot_cols, dim3((unsigned)cdiv(n_edges, 256)), dim3(256), 0, stream, col,
+                     n_edges, mask, n_src, col_hot);
+  return check_launch("k_hot_cols");
+}
+
+}  // extern "C"

@@ -15,8 +15,10 @@
 #include "hgnn_common.h"
 
 // Cache policy of the gathered rows and the output rows (set per launch from the table sizes,
-// `nt_policy` below): nt loads / stores when the table is far larger than the caches.
+// `nt_policy` / `hot_policy` below): nt loads / stores when the table is far larger than the
+// caches; with a col_hot, nt loads for all but the relation's most referenced rows.
 #include <stdlib.h>
+#include <string.h>
 
 namespace hgnn {
 
@@ -51,13 +53,24 @@ struct GatherArgs {
   int32_t nt_load;             // rows gathered with nt loads (score gathers over multi-GB tables)
   int32_t nt_store;            // output rows stored with nt stores
   const int32_t* col2;
+  int32_t hot;                 // col holds hot flags in bit 31 (hgnn_hot_cols): two-policy loads
 };
+
+// bit 31 of a col_hot entry: the source row is one of the relation's H most referenced rows
+constexpr int32_t kHotIdMask = 0x7fffffff;
 
 // Sum of row segment [beg, end) of `col` into acc (per lane: VPL vectors of width W; each slot of
 // LPR lanes holds its own partial sum, combined by slot_combine).  SC: the weight of each edge is
 // recomputed from the score <x[col[p]], rv> (rv = the row's own vector, e.g. P[post] for the loss
 // gradient dP) with weight mode `score`, so no per-edge weight array is stored or read.
-template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC>
+//
+// HOT: `col` is a col_hot array.  A flagged (hot) row is read with the default policy and stays
+// cacheable; every other row is read nt, so the long tail of rows referenced once or twice no
+// longer pushes the Zipf head out of L2 and the Infinity Cache.  The flag is uniform per slot of
+// LPR lanes; both loads of a vector sit in one diamond on it, issued before anything waits, as
+// the bounds-predicated load of the plain kernel is (ISA: the UNROLL rows' loads, then one
+// s_waitcnt vmcnt(0), in both kernels).
+template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC, bool HOT>
 __device__ __forceinline__ void segment_sum(const GatherArgs& a, const int32_t* col, int score,
                                             int64_t beg, int64_t end,
                                             const typename Vec<W>::T (&rv)[VPL],
@@ -75,7 +88,7 @@ __device__ __forceinline__ void segment_sum(const GatherArgs& a, const int32_t* 
       cidx = col[base + lane];
       if (HAS_W) {
         wv = a.edge_w ? a.edge_w[base + lane] : 1.f;
-        if (a.col_w) wv *= a.col_w[cidx];
+        if (a.col_w) wv *= a.col_w[HOT ? cidx & kHotIdMask : cidx];
       }
     }
     for (int j = 0; j < n; j += NS * UNROLL) {
@@ -84,7 +97,9 @@ __device__ __forceinline__ void segment_sum(const GatherArgs& a, const int32_t* 
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) {
         const int e = j + u * NS + slot;
-        const int src = __shfl(cidx, e & 63, 64);
+        const int raw = __shfl(cidx, e & 63, 64);
+        const int src = HOT ? raw & kHotIdMask : raw;
+        const bool cold = HOT && raw >= 0;
         we[u] = HAS_W ? __shfl(wv, e & 63, 64) : 1.f;
         const float* xr = a.x + (int64_t)src * d;
 #pragma unroll
@@ -96,6 +111,8 @@ __device__ __forceinline__ void segment_sum(const GatherArgs& a, const int32_t* 
           // the source-block passes and the Zipf-hot post rows live on cache reuse)
           if (SC && a.nt_load)
             v[u][q] = (e < n && c < d) ? V::load_nt(xr + c) : V::zero();
+          else if (HOT)
+            v[u][q] = (e < n && c < d) ? (cold ? V::load_nt(xr + c) : V::load(xr + c)) : V::zero();
           else
             v[u][q] = (e < n && c < d) ? V::load(xr + c) : V::zero();
         }
@@ -134,7 +151,7 @@ __device__ __forceinline__ void slot_combine(typename Vec<W>::T (&acc)[VPL]) {
 }
 
 // one item (a light row, or a chunk of a heavy row) per wave
-template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC>
+template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC, bool HOT = false>
 __device__ __forceinline__ void gather_item(const GatherArgs& a, const int64_t item) {
   using V = Vec<W>;
   const int lane = threadIdx.x & 63;
@@ -176,10 +193,10 @@ __device__ __forceinline__ void gather_item(const GatherArgs& a, const int64_t i
     const int c = (q * LPR + sl) * W;
     rv[q] = (SC && c < a.d) ? V::load(a.rowvec + row * a.d + c) : V::zero();
   }
-  if (own) segment_sum<LPR, VPL, W, UNROLL, HAS_W, SC>(a, a.col, a.score, beg, end, rv, acc);
+  if (own) segment_sum<LPR, VPL, W, UNROLL, HAS_W, SC, HOT>(a, a.col, a.score, beg, end, rv, acc);
   if (two && !partial)
-    segment_sum<LPR, VPL, W, UNROLL, HAS_W, SC>(a, a.col2, 2, a.rowptr2[row], a.rowptr2[row + 1],
-                                                rv, acc);
+    segment_sum<LPR, VPL, W, UNROLL, HAS_W, SC, false>(a, a.col2, 2, a.rowptr2[row],
+                                                       a.rowptr2[row + 1], rv, acc);
   slot_combine<LPR, VPL, W>(acc);
   if (!writer) return;
   float s = 1.f;
@@ -202,11 +219,11 @@ __device__ __forceinline__ void gather_item(const GatherArgs& a, const int64_t i
   }
 }
 
-template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC = false>
+template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC = false, bool HOT = false>
 __global__ void __launch_bounds__(256) k_gather(const GatherArgs a) {
   const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (item >= a.n_items) return;
-  gather_item<LPR, VPL, W, UNROLL, HAS_W, SC>(a, item);
+  gather_item<LPR, VPL, W, UNROLL, HAS_W, SC, HOT>(a, item);
 }
 
 // Several gathers of one row width in one launch (hgnn_gather_reduce_multi): job j owns the
@@ -274,7 +291,8 @@ __global__ void __launch_bounds__(256) k_fixup(const GatherArgs a) {
       typename V::T t = buf[threadIdx.x];
       V::scale(t, s);
       float* o = a.out + row * a.d + c;
-      if (a.accumulate || a.rowptr2) V::add(t, V::load(o));
+      if ((a.accumulate && (a.acc_limit == 0 || row < a.acc_limit)) || a.rowptr2)
+        V::add(t, V::load(o));
       V::store(o, t);
     }
     __syncthreads();
@@ -286,6 +304,12 @@ static int launch_gather(const GatherArgs& a, bool has_w, hipStream_t stream) {
   const dim3 grid((unsigned)cdiv(a.n_items, 4)), block(256);
   if (a.score)
     hipLaunchKernelGGL((k_gather<LPR, VPL, W, UNROLL, false, true>), grid, block, 0, stream, a);
+  else if (a.hot && has_w)   // the two-policy loads as their own instantiations (hot_policy)
+    hipLaunchKernelGGL((k_gather<LPR, VPL, W, UNROLL, true, false, true>), grid, block, 0, stream,
+                       a);
+  else if (a.hot)
+    hipLaunchKernelGGL((k_gather<LPR, VPL, W, UNROLL, false, false, true>), grid, block, 0,
+                       stream, a);
   else if (has_w)
     hipLaunchKernelGGL((k_gather<LPR, VPL, W, UNROLL, true>), grid, block, 0, stream, a);
   else
@@ -307,6 +331,10 @@ static int dispatch_gather(const GatherArgs& a, bool has_w, hipStream_t stream) 
       const dim3 grid((unsigned)cdiv(a.n_items, 4)), block(256);
       if (a.score)
         hipLaunchKernelGGL((k_gather<16, 1, 4, 4, false, true>), grid, block, 0, stream, a);
+      else if (a.hot && has_w)
+        hipLaunchKernelGGL((k_gather<16, 1, 4, 6, true, false, true>), grid, block, 0, stream, a);
+      else if (a.hot)
+        hipLaunchKernelGGL((k_gather<16, 1, 4, 8, false, false, true>), grid, block, 0, stream, a);
       else if (has_w)
         hipLaunchKernelGGL((k_gather<16, 1, 4, 6, true>), grid, block, 0, stream, a);
       else
@@ -335,6 +363,26 @@ constexpr int64_t kNtBytes = int64_t(1) << 30;
 static void nt_policy(GatherArgs& a, int64_t n_x) {
   a.nt_load = a.score && n_x * a.d * 4 >= kNtBytes ? 1 : 0;
   a.nt_store = (a.score ? a.nt_load : a.n_rows * a.d * 4 >= kNtBytes) ? 1 : 0;
+}
+
+// Two-policy loads (col_hot): on when the table outgrows the Infinity Cache (the scoring pass's
+// nt_neg threshold), the caller passed a col_hot, and the flagged rows carry at least half of
+// the edges.  Measured at cfg4 (512-MB post table, Zipf(0.8) ids, K1 / K2 user<-post, policy off
+// 11.49 / 11.63 ms): flagging the 32768 .. 131072 most referenced rows (48 - 65 % of the edges)
+// gives 10.70 - 10.88 / 10.87 - 11.03 ms, 16384 rows (41 %) 11.03 / 11.21, 8192 rows (35 %) no
+// gain and 4096 rows (29 %) a loss (12.05 / 12.23): an nt row loses the Infinity Cache as well
+// as L2, so the cold set must be the tail that neither cache would have kept.  Below half of the
+// edges the rule keeps the old kernel.  HGNN_HOT_ROWS=0 turns the policy off,
+// HGNN_HOT_ROWS=force on for any table that comes with a col_hot (tests).  Read per call: a
+// getenv against a 10-ms kernel.
+constexpr int64_t kHotTableBytes = int64_t(256) << 20;
+constexpr float kHotShareMin = 0.5f;
+static bool hot_policy(int64_t table_bytes, bool has_col_hot, float hot_share) {
+  if (!has_col_hot) return false;
+  const char* e = getenv("HGNN_HOT_ROWS");
+  if (e && !strcmp(e, "0")) return false;
+  if (e && !strcmp(e, "force")) return true;
+  return table_bytes >= kHotTableBytes && hot_share >= kHotShareMin;
 }
 
 static int run_gather(GatherArgs a, hipStream_t stream) {
@@ -379,6 +427,32 @@ int hgnn_gather_reduce(const float* x, int64_t n_x, int32_t d, const int32_t* ro
   a.d = d; a.chunk = chunk; a.mean = (flags & HGNN_MEAN) ? 1 : 0;
   a.accumulate = (flags & HGNN_ACCUMULATE) ? 1 : 0;
   nt_policy(a, n_x);
+  return run_gather(a, as_stream(stream));
+}
+
+int32_t hgnn_hot_rows_policy(int64_t table_bytes, int32_t has_col_hot, float hot_share) {
+  return hot_policy(table_bytes, has_col_hot != 0, hot_share) ? 1 : 0;
+}
+
+int hgnn_gather_reduce_hot(const float* x, int64_t n_x, int32_t d, const int32_t* rowptr,
+                           const int32_t* col, int64_t n_rows, const float* edge_w,
+                           const float* col_w, int32_t flags, const int32_t* heavy_rows,
+                           const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
+                           int32_t chunk, float* slab, float* out, int64_t acc_limit,
+                           const int32_t* col_hot, float hot_share, hgnn_stream_t stream) {
+  if (acc_limit < 0) return fail(HGNN_E_ARG, "gather_reduce_hot: acc_limit < 0");
+  GatherArgs a{};
+  a.x = x; a.rowptr = rowptr; a.col = col; a.edge_w = edge_w; a.col_w = col_w;
+  a.heavy_rows = heavy_rows; a.heavy_first = heavy_first; a.slab = slab; a.out = out;
+  a.n_rows = n_rows; a.n_heavy = n_heavy; a.n_items = n_rows + (n_heavy > 0 ? n_chunks : 0);
+  a.d = d; a.chunk = chunk; a.mean = (flags & HGNN_MEAN) ? 1 : 0;
+  a.accumulate = (flags & HGNN_ACCUMULATE) ? 1 : 0;
+  a.acc_limit = acc_limit;
+  nt_policy(a, n_x);
+  if (hot_policy(n_x * (int64_t)d * 4, col_hot != nullptr, hot_share)) {
+    a.col = col_hot;
+    a.hot = 1;
+  }
   return run_gather(a, as_stream(stream));
 }
 

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import collections
 import dataclasses
+import os
 import weakref
 from typing import Dict, Optional, Tuple
 
@@ -149,6 +150,46 @@ def _plan(rowptr: torch.Tensor, n_rows: int, chunk: int) -> Plan:
     N.check(lib.hgnn_plan_fill(N.ptr(rowptr), n_rows, chunk, N.ptr(heavy_rows),
                                N.ptr(heavy_first), N.ptr(ws), ws.numel(), s), "hgnn_plan_fill")
     return Plan(chunk, n_heavy, n_chunks, heavy_rows, heavy_first)
+
+
+# ----------------------------------------------------------------------------- hot-row flags
+# Default number of flagged rows per relation (HGNN_HOT_ROWS_H overrides).  Chosen by the cfg4
+# sweep: K1 / K2 user<-post are fastest with 49152 - 65536 hot rows of the 1M (32 MiB
+# of 512-B rows, 52 - 56 % of the edges) and flat between 32768 and 98304.
+HOT_ROWS_H = 65536
+
+
+def hot_rows_h() -> int:
+    return int(os.environ.get("HGNN_HOT_ROWS_H", HOT_ROWS_H))
+
+
+@dataclasses.dataclass
+class HotCols:
+    """A grouping's ``col`` with bit 31 set on its ``h`` most referenced source rows
+    (``hgnn_hot_cols``), and those rows' share of the edges.  ``col`` is None once the share
+    turned out too small for the policy (``hgnn_hot_rows_policy``): only the share is kept."""
+    col: Optional[torch.Tensor]
+    share: float
+    h: int
+
+
+def build_hot_cols(grouped: GroupedEdges, deg_rowptr: torch.Tensor, n_read: int,
+                   h: int) -> HotCols:
+    """``hgnn_hot_cols`` over ``grouped.col`` (ids of a table of ``n_read`` rows whose reference
+    counts are ``deg_rowptr``'s segment lengths: the opposite grouping's rowptr)."""
+    if n_read > 2**31:
+        raise ValueError(f"hot_cols: {n_read} rows: ids must stay below 2^31 (bit 31 is the flag)")
+    dev = N.require_device(grouped.col, deg_rowptr)
+    E = int(grouped.col.numel())
+    lib = N.lib()
+    col_hot = torch.empty(E, dtype=torch.int32, device=dev)
+    hot_edges = torch.empty(1, dtype=torch.int64, device=dev)
+    ws = N.workspace(lib.hgnn_hot_cols_ws_bytes(n_read), dev)
+    N.check(lib.hgnn_hot_cols(N.ptr(deg_rowptr), n_read, N.ptr(grouped.col), E, int(h),
+                              N.ptr(col_hot), N.ptr(hot_edges), N.ptr(ws), ws.numel(),
+                              N.stream_ptr(dev)), "hgnn_hot_cols")
+    share = int(hot_edges.item()) / E if E else 0.0   # host sync: once per graph
+    return HotCols(col_hot, share, int(h))
 
 
 def group_edges(key: torch.Tensor, other: torch.Tensor, n_keys: int, n_other: int,
@@ -310,6 +351,32 @@ class RelationCSR:
                 torch.empty(0, dtype=torch.float32, device=self.inv_deg.device)
             self._bwd_w = w
         return w
+
+    def hot_cols(self, side: str, table_bytes: int) -> Optional[HotCols]:
+        """The hot-flagged ``col`` of the ``"fwd"`` / ``"bwd"`` grouping for a gather that reads
+        a table of ``table_bytes``, or None where the two-policy loads are off by rule
+        (``hgnn_hot_rows_policy``: small table, ``HGNN_HOT_ROWS=0``, too small a hot share).
+        Built on first use and kept on the grouping as ``_uop`` is (4 B per edge: 0.8 GB per
+        grouping at cfg4); the reference counts come from the opposite grouping's rowptr.  Never
+        for a sampled block (``from_csr``) and never built inside a stream capture."""
+        if getattr(self, "_from_csr", False) or self.num_edges == 0:
+            return None
+        lib = N.lib()
+        if not lib.hgnn_hot_rows_policy(int(table_bytes), 1, 1.0):
+            return None
+        g, n_read = (self.fwd, self.n_src) if side == "fwd" else (self.bwd, self.n_dst)
+        h = hot_rows_h()
+        hc = g.__dict__.get("_hot")
+        if hc is None or hc.h != h or (hc.col is None and
+                                       lib.hgnn_hot_rows_policy(int(table_bytes), 1, hc.share)):
+            if g.col.is_cuda and torch.cuda.is_current_stream_capturing():
+                return None
+            opposite = self.bwd if side == "fwd" else self.fwd
+            hc = build_hot_cols(g, opposite.rowptr, n_read, h)
+            if not lib.hgnn_hot_rows_policy(int(table_bytes), 1, hc.share):
+                hc.col = None
+            g._hot = hc
+        return hc if hc.col is not None else None
 
     def blocks(self, side: str, n_blocks: int):
         """The relation split into ``n_blocks`` passes over contiguous blocks of the table a

@@ -313,7 +313,8 @@ def gather_mean(x_src: torch.Tensor, csr: RelationCSR,
                         gather_bytes(E, csr.n_dst, d, False),
                         gather_compulsory_bytes(E, csr.n_dst, csr.n_src, d, False))
         return out
-    _gather(x_src, csr.fwd, None, csr_mean=True, out=out, accumulate=acc)
+    _gather(x_src, csr.fwd, None, csr_mean=True, out=out, accumulate=acc,
+            hot=csr.hot_cols("fwd", _table_bytes(x_src)))
     return out
 
 
@@ -380,7 +381,13 @@ def gather_mean_many(pairs: Sequence[Tuple[torch.Tensor, RelationCSR]],
     return [o for _, _, o in jobs]
 
 
-def _gather(x, grouped, col_w, csr_mean, out, accumulate, edge_w=None, kind=None):
+def _table_bytes(x: torch.Tensor) -> int:
+    return x.numel() * x.element_size()
+
+
+def _gather(x, grouped, col_w, csr_mean, out, accumulate, edge_w=None, kind=None, hot=None):
+    """``hot``: the grouping's ``graph.HotCols`` (``RelationCSR.hot_cols``) or None; with one the
+    launch goes through ``hgnn_gather_reduce_hot`` (two-policy row loads, same sums)."""
     p = grouped.plan
     dev = out.device
     slab = None
@@ -394,6 +401,13 @@ def _gather(x, grouped, col_w, csr_mean, out, accumulate, edge_w=None, kind=None
     E = int(grouped.col.numel())
     with _timed(name, gather_bytes(E, grouped.n_rows, d, weighted),
                 gather_compulsory_bytes(E, grouped.n_rows, int(x.shape[0]), d, weighted)):
+        if hot is not None:
+            N.check(N.lib().hgnn_gather_reduce_hot(
+                N.ptr(x), x.shape[0], d, N.ptr(grouped.rowptr), N.ptr(grouped.col),
+                grouped.n_rows, N.ptr(edge_w), N.ptr(col_w), flags, N.ptr(p.heavy_rows),
+                N.ptr(p.heavy_first), p.n_heavy, p.n_chunks, p.chunk, N.ptr(slab), N.ptr(out),
+                0, N.ptr(hot.col), hot.share, N.stream_ptr(dev)), "hgnn_gather_reduce_hot")
+            return
         N.check(N.lib().hgnn_gather_reduce(
             N.ptr(x), x.shape[0], d, N.ptr(grouped.rowptr), N.ptr(grouped.col),
             grouped.n_rows, N.ptr(edge_w), N.ptr(col_w), flags, N.ptr(p.heavy_rows),
@@ -462,7 +476,7 @@ def scatter_mean_bwd(grad_aggr: torch.Tensor, csr: RelationCSR,
                         gather_compulsory_bytes(E, csr.n_src, csr.n_dst, d, True))
         return out
     _gather(grad_aggr, csr.bwd, None, csr_mean=False, out=out, accumulate=acc,
-            edge_w=csr.bwd_weights)
+            edge_w=csr.bwd_weights, hot=csr.hot_cols("bwd", _table_bytes(grad_aggr)))
     return out
 
 
@@ -1560,6 +1574,8 @@ def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total:
             on_dP(dP)
     if ready is not None and p_chunks is not None:
         ready()                                 # all of P, for the scoring pass
+    # (The scoring pass takes no col_hot: with the positives' cold rows read nt it measured
+    # 29-33 ms against 25.4 at cfg4 for every H tried)
     with _timed(f"edge_score_d{d}", 4 * E * (2 * d + 1 + 2) + 8 * nu * d):
         if draw is not None:
             N.check(lib.hgnn_edge_score_fwd_draw(
