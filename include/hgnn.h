@@ -436,6 +436,53 @@ int hgnn_uniform_i32(const uint64_t* d_seed, int64_t n, int32_t hi, int32_t* out
  * gradient (1 for loss.backward()).  x 16-byte aligned. */
 int hgnn_scale_unless_one(float* x, int64_t n, const float* d_scale, hgnn_stream_t stream);
 
+/* ---- bf16 row storage (opt-in: HGNN_ROW_DTYPE=bf16 in the Python layer) ------------------------
+ * The forward gathers and the link loss read one row per edge from a table that is a layer
+ * output.  In this mode they read a bf16 copy of it (half the bytes) and widen each element to
+ * fp32 where it is summed; accumulators, outputs, gradients and everything else stay fp32.  A
+ * result equals what the fp32 entry point gives on the table R(T) = float(bf16(T)), up to fp32
+ * summation order (the lane mapping differs).  bf16 tables cross the boundary as uint16_t,
+ * 16-byte aligned, row-major [n, d] with d % 8 == 0.  No atomics; bitwise reproducible. */
+
+/* out[i] = bf16(x[i]), round to nearest even (bitwise torch's float -> bfloat16 for every
+ * non-NaN value; NaN -> 0x7fc0).  A streaming pass with 16-B accesses and a tail for
+ * n_elems % 8; n_elems = 0 is fine.  x and out 16-byte aligned. */
+int hgnn_rows_to_bf16(const float* x, int64_t n_elems, uint16_t* out, hgnn_stream_t stream);
+
+/* hgnn_gather_reduce_hot and hgnn_gather_reduce_scaled in one, over a bf16 source table x:
+ * edge_w / col_w / row_w (row_w replaces HGNN_MEAN, not both), HGNN_MEAN / HGNN_ACCUMULATE,
+ * acc_limit, the heavy-row plan with its fp32 slab, col_hot / hot_share (all nullable as there).
+ * out is fp32.  The cache policies take the table's real size, n_x * d * 2 bytes.  d % 8 == 0
+ * and d <= 1024, else HGNN_E_UNSUPPORTED (the message names d). */
+int hgnn_gather_reduce_bf16(const uint16_t* x, int64_t n_x, int32_t d, const int32_t* rowptr,
+                            const int32_t* col, int64_t n_rows, const float* edge_w,
+                            const float* col_w, const float* row_w, int32_t flags,
+                            const int32_t* heavy_rows, const int32_t* heavy_first,
+                            int64_t n_heavy, int64_t n_chunks, int32_t chunk, float* slab,
+                            float* out, int64_t acc_limit, const int32_t* col_hot,
+                            float hot_share, hgnn_stream_t stream);
+
+/* hgnn_score_gather2 with x (U) and rowvec (P) both bf16; fp32 out.  Same d rule. */
+int hgnn_score_gather2_bf16(const uint16_t* x, int64_t n_x, const uint16_t* rowvec, int32_t d,
+                            const int32_t* rowptr, const int32_t* col, const int32_t* rowptr_n,
+                            const int32_t* col_n, int64_t n_rows, const float* cscale,
+                            float inv_e, const int32_t* heavy_rows, const int32_t* heavy_first,
+                            int64_t n_heavy, int64_t n_chunks, int32_t chunk, float* slab,
+                            float* out, hgnn_stream_t stream);
+
+/* The scoring pass (hgnn_edge_score_fwd) with bf16 U and P: the score <U[u], P[p]> is the same
+ * number here and in hgnn_score_gather2_bf16.  The negatives come in exactly one of the three
+ * forms of the fp32 entries: neg_i64 (hgnn_edge_score_fwd), neg_i32 (.._i32) or d_seed (.._draw:
+ * the draws hgnn_uniform_i32 makes); the other two NULL.  fp32 dU, part, loss and err as there;
+ * the optional per-position outputs (hpos, neg_key, neg_w) are not produced.  d % 8 == 0 and
+ * d <= 512, else HGNN_E_UNSUPPORTED. */
+int hgnn_edge_score_fwd_bf16(const uint16_t* U, const uint16_t* P, int32_t d, int64_t n_users,
+                             int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
+                             const int64_t* neg_i64, const int32_t* neg_i32,
+                             const uint64_t* d_seed, int64_t n_edges, const float* cscale,
+                             float* dU, float* part, float* loss, int32_t* err,
+                             hgnn_stream_t stream);
+
 /* ---- neighbour sampling for mini-batches (BASELINE cfg5; no reference counterpart) -----------
  * For each destination dst_ids[i] (rows of a destination-grouped CSR rowptr/col over n_rows):
  * keep all in-neighbours if deg <= fanout (or fanout < 0), else `fanout` distinct neighbour

@@ -1,6 +1,11 @@
 """hgnn on MI355X: the hetero SAGE message-passing hot path of ramkp990/Truth_Recommendation_GNN,
 rebuilt as hand-written gfx950 HIP kernels behind a C ABI (``include/hgnn.h``), with the
 reference's PyG-style Python surface (``SAGEConv``, ``HeteroData``, ``WeightedRGCN``).
+
+fp32 throughout by default.  ``HGNN_ROW_DTYPE=bf16`` (read at import into ``ops.ROW_DTYPE``), or
+``row_dtype="bf16"`` on the models, ``ops.LayerSpec`` and ``ops.edge_bce_loss``, stores the rows
+the forward gathers and the link loss read per edge as bf16 (``ops.rows_to_bf16``); everything
+else stays fp32.
 """
 from .graph import HeteroData, RelationCSR, relation_csr, CSR_CACHE  # noqa: F401
 from .nn import SAGEConv, WeightedRGCN, WeightedRGCNAuthor, HeteroSAGE  # noqa: F401

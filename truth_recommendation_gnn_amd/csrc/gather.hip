@@ -23,7 +23,7 @@
 namespace hgnn {
 
 struct GatherArgs {
-  const float* x;
+  const void* x;               // source table: fp32 rows, or bf16 rows when `bf16` is set
   const int32_t* rowptr;
   const int32_t* col;
   const float* edge_w;
@@ -43,7 +43,7 @@ struct GatherArgs {
   int64_t acc_limit;           // > 0: only rows below it accumulate, the others are written
                                // fresh (a K2 whose output holds a root-gradient prefix)
   // score mode (hgnn_score_gather): w_p = f(<x[col[p]], rowvec[row]>) recomputed per edge
-  const float* rowvec;
+  const void* rowvec;          // (of the source table's element type)
   const float* cscale;
   float inv_e;
   int32_t score;               // 1: c*inv_e*(sigmoid(s)-1)   2: inv_e*sigmoid(s)
@@ -54,6 +54,7 @@ struct GatherArgs {
   int32_t nt_store;            // output rows stored with nt stores
   const int32_t* col2;
   int32_t hot;                 // col holds hot flags in bit 31 (hgnn_hot_cols): two-policy loads
+  int32_t bf16;                // x (and rowvec) hold bf16 rows: the XT = uint16_t instantiations
 };
 
 // bit 31 of a col_hot entry: the source row is one of the relation's H most referenced rows
@@ -70,12 +71,17 @@ constexpr int32_t kHotIdMask = 0x7fffffff;
 // LPR lanes; both loads of a vector sit in one diamond on it, issued before anything waits, as
 // the bounds-predicated load of the plain kernel is (ISA: the UNROLL rows' loads, then one
 // s_waitcnt vmcnt(0), in both kernels).
-template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC, bool HOT>
+//
+// XT: the source table's element type (RowSrc).  A bf16 row is read 16 B per lane, so d = 128 is
+// 16 lanes per row and 4 rows per wave load; its vectors stay packed while in flight and are
+// widened to fp32 where they are summed.  Everything after the load is fp32 either way.
+template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC, bool HOT, typename XT = float>
 __device__ __forceinline__ void segment_sum(const GatherArgs& a, const int32_t* col, int score,
                                             int64_t beg, int64_t end,
                                             const typename Vec<W>::T (&rv)[VPL],
                                             typename Vec<W>::T (&acc)[VPL]) {
   using V = Vec<W>;
+  using S = RowSrc<XT, W>;
   constexpr int NS = 64 / LPR;
   const int lane = threadIdx.x & 63;
   const int slot = lane / LPR, sl = lane % LPR;
@@ -92,7 +98,7 @@ __device__ __forceinline__ void segment_sum(const GatherArgs& a, const int32_t* 
       }
     }
     for (int j = 0; j < n; j += NS * UNROLL) {
-      typename V::T v[UNROLL][VPL];
+      typename S::Raw v[UNROLL][VPL];
       float we[UNROLL];
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) {
@@ -101,7 +107,7 @@ __device__ __forceinline__ void segment_sum(const GatherArgs& a, const int32_t* 
         const int src = HOT ? raw & kHotIdMask : raw;
         const bool cold = HOT && raw >= 0;
         we[u] = HAS_W ? __shfl(wv, e & 63, 64) : 1.f;
-        const float* xr = a.x + (int64_t)src * d;
+        const XT* xr = static_cast<const XT*>(a.x) + (int64_t)src * d;
 #pragma unroll
         for (int q = 0; q < VPL; ++q) {
           const int c = (q * LPR + sl) * W;
@@ -110,11 +116,11 @@ __device__ __forceinline__ void segment_sum(const GatherArgs& a, const int32_t* 
           // only above 1 GiB); the mean gathers keep the default policy (nt costs them 25-45 %:
           // the source-block passes and the Zipf-hot post rows live on cache reuse)
           if (SC && a.nt_load)
-            v[u][q] = (e < n && c < d) ? V::load_nt(xr + c) : V::zero();
+            v[u][q] = (e < n && c < d) ? S::load_nt(xr + c) : S::zero();
           else if (HOT)
-            v[u][q] = (e < n && c < d) ? (cold ? V::load_nt(xr + c) : V::load(xr + c)) : V::zero();
+            v[u][q] = (e < n && c < d) ? (cold ? S::load_nt(xr + c) : S::load(xr + c)) : S::zero();
           else
-            v[u][q] = (e < n && c < d) ? V::load(xr + c) : V::zero();
+            v[u][q] = (e < n && c < d) ? S::load(xr + c) : S::zero();
         }
       }
       if constexpr (SC) {
@@ -123,7 +129,7 @@ __device__ __forceinline__ void segment_sum(const GatherArgs& a, const int32_t* 
         for (int u = 0; u < UNROLL; ++u) {
           float sdot = 0.f;
 #pragma unroll
-          for (int q = 0; q < VPL; ++q) sdot += V::dot(rv[q], v[u][q]);
+          for (int q = 0; q < VPL; ++q) sdot += V::dot(rv[q], S::widen(v[u][q]));
           sdot = slot_sum<LPR>(sdot);
           const float sg = sigmoid_t(sdot, exp_neg_abs(sdot));
           we[u] = cw * (score == 1 ? sg - 1.f : sg);
@@ -133,8 +139,8 @@ __device__ __forceinline__ void segment_sum(const GatherArgs& a, const int32_t* 
       for (int u = 0; u < UNROLL; ++u)
 #pragma unroll
         for (int q = 0; q < VPL; ++q) {
-          if (HAS_W || SC) V::fma(acc[q], we[u], v[u][q]);
-          else V::add(acc[q], v[u][q]);
+          if (HAS_W || SC) V::fma(acc[q], we[u], S::widen(v[u][q]));
+          else V::add(acc[q], S::widen(v[u][q]));
         }
     }
   }
@@ -151,9 +157,11 @@ __device__ __forceinline__ void slot_combine(typename Vec<W>::T (&acc)[VPL]) {
 }
 
 // one item (a light row, or a chunk of a heavy row) per wave
-template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC, bool HOT = false>
+template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC, bool HOT = false,
+          typename XT = float>
 __device__ __forceinline__ void gather_item(const GatherArgs& a, const int64_t item) {
   using V = Vec<W>;
+  using S = RowSrc<XT, W>;
   const int lane = threadIdx.x & 63;
   const int sl = lane % LPR;
   const bool writer = lane < LPR;
@@ -191,12 +199,15 @@ __device__ __forceinline__ void gather_item(const GatherArgs& a, const int64_t i
   for (int q = 0; q < VPL; ++q) {
     acc[q] = V::zero();
     const int c = (q * LPR + sl) * W;
-    rv[q] = (SC && c < a.d) ? V::load(a.rowvec + row * a.d + c) : V::zero();
+    rv[q] = (SC && c < a.d)
+                ? S::widen(S::load(static_cast<const XT*>(a.rowvec) + row * a.d + c))
+                : V::zero();
   }
-  if (own) segment_sum<LPR, VPL, W, UNROLL, HAS_W, SC, HOT>(a, a.col, a.score, beg, end, rv, acc);
+  if (own)
+    segment_sum<LPR, VPL, W, UNROLL, HAS_W, SC, HOT, XT>(a, a.col, a.score, beg, end, rv, acc);
   if (two && !partial)
-    segment_sum<LPR, VPL, W, UNROLL, HAS_W, SC, false>(a, a.col2, 2, a.rowptr2[row],
-                                                       a.rowptr2[row + 1], rv, acc);
+    segment_sum<LPR, VPL, W, UNROLL, HAS_W, SC, false, XT>(a, a.col2, 2, a.rowptr2[row],
+                                                           a.rowptr2[row + 1], rv, acc);
   slot_combine<LPR, VPL, W>(acc);
   if (!writer) return;
   float s = 1.f;
@@ -219,11 +230,12 @@ __device__ __forceinline__ void gather_item(const GatherArgs& a, const int64_t i
   }
 }
 
-template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC = false, bool HOT = false>
+template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC = false, bool HOT = false,
+          typename XT = float>
 __global__ void __launch_bounds__(256) k_gather(const GatherArgs a) {
   const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (item >= a.n_items) return;
-  gather_item<LPR, VPL, W, UNROLL, HAS_W, SC, HOT>(a, item);
+  gather_item<LPR, VPL, W, UNROLL, HAS_W, SC, HOT, XT>(a, item);
 }
 
 // Several gathers of one row width in one launch (hgnn_gather_reduce_multi): job j owns the
@@ -356,12 +368,57 @@ static int dispatch_gather(const GatherArgs& a, bool has_w, hipStream_t stream) 
   return fail(HGNN_E_UNSUPPORTED, "gather: d=%d > 1024", d);
 }
 
+// bf16 source rows (W = 8, 16 B per lane): the same five variants, rows in flight per wave
+// (64 / LPR x the depth) per variant: UM the mean / plain sum, UW weighted, US the score gather.
+template <int LPR, int VPL, int UM, int UW, int US>
+static int launch_gather_bf16(const GatherArgs& a, bool has_w, hipStream_t stream) {
+  using B = uint16_t;
+  const dim3 grid((unsigned)cdiv(a.n_items, 4)), block(256);
+  if (a.score)
+    hipLaunchKernelGGL((k_gather<LPR, VPL, 8, US, false, true, false, B>), grid, block, 0, stream,
+                       a);
+  else if (a.hot && has_w)
+    hipLaunchKernelGGL((k_gather<LPR, VPL, 8, UW, true, false, true, B>), grid, block, 0, stream,
+                       a);
+  else if (a.hot)
+    hipLaunchKernelGGL((k_gather<LPR, VPL, 8, UM, false, false, true, B>), grid, block, 0, stream,
+                       a);
+  else if (has_w)
+    hipLaunchKernelGGL((k_gather<LPR, VPL, 8, UW, true, false, false, B>), grid, block, 0, stream,
+                       a);
+  else
+    hipLaunchKernelGGL((k_gather<LPR, VPL, 8, UM, false, false, false, B>), grid, block, 0,
+                       stream, a);
+  return check_launch("k_gather(bf16)");
+}
+
+// The depths are the fp32 kernels' rows in flight at the same d (d = 64: 32 / 24 / 16 rows,
+// d = 128: 8).  At d = 128 twice that (16 rows, the fp32 kernel's BYTES in flight) measured the
+// same at cfg4 (K1 post<-user 7.64 - 7.77 ms at 8 rows, 7.58 - 7.59 at 16; the dP gather 15.73 -
+// 15.99 against 15.68 - 16.28; the step 89.7 - 90.0 against 89.0 - 90.1 ms): 8 kept, the form
+// with fewer registers held; the deeper one is no longer built.
+static int dispatch_gather_bf16(const GatherArgs& a, bool has_w, hipStream_t stream) {
+  const int d = a.d;
+  if (d % 8 != 0 || d > 1024)
+    return fail(HGNN_E_UNSUPPORTED, "gather(bf16 rows): d=%d (needs d %% 8 == 0 and d <= 1024)", d);
+  const int nv = d / 8;  // 16-B vectors per row
+  if (nv <= 2) return launch_gather_bf16<2, 1, 2, 2, 2>(a, has_w, stream);
+  if (nv <= 4) return launch_gather_bf16<4, 1, 4, 4, 4>(a, has_w, stream);
+  if (nv <= 8) return launch_gather_bf16<8, 1, 4, 3, 2>(a, has_w, stream);
+  if (nv <= 16) return launch_gather_bf16<16, 1, 2, 2, 2>(a, has_w, stream);
+  if (nv <= 32) return launch_gather_bf16<32, 1, 4, 4, 4>(a, has_w, stream);
+  if (nv <= 64) return launch_gather_bf16<64, 1, 4, 4, 4>(a, has_w, stream);
+  return launch_gather_bf16<64, 2, 2, 2, 2>(a, has_w, stream);
+}
+
 // nt above 1 GiB: cfg4's 4.6 GB user table and its 4.6 GB user-side outputs.  Output rows of
 // the dP gather / K2s / means are read by another kernel long after they left L2 (cfg4 step
 // 168.1 -> 167.5 ms with nt stores, mostly the dP gather); cfg2/cfg3 tables stay cache-resident.
 constexpr int64_t kNtBytes = int64_t(1) << 30;
-static void nt_policy(GatherArgs& a, int64_t n_x) {
-  a.nt_load = a.score && n_x * a.d * 4 >= kNtBytes ? 1 : 0;
+// (`elem`: bytes per element of the source table, so the threshold sees the table's real size;
+// the output rows are fp32 either way)
+static void nt_policy(GatherArgs& a, int64_t n_x, int64_t elem = 4) {
+  a.nt_load = a.score && n_x * a.d * elem >= kNtBytes ? 1 : 0;
   a.nt_store = (a.score ? a.nt_load : a.n_rows * a.d * 4 >= kNtBytes) ? 1 : 0;
 }
 
@@ -399,7 +456,8 @@ static int run_gather(GatherArgs a, hipStream_t stream) {
     return fail(HGNN_E_ARG, "score_gather: bad mode/arguments");
   if (a.rowptr2 && a.score != 1)
     return fail(HGNN_E_ARG, "score_gather2: needs mode 1 for the first list");
-  if (int rc = dispatch_gather(a, has_w, stream)) return rc;
+  if (int rc = a.bf16 ? dispatch_gather_bf16(a, has_w, stream) : dispatch_gather(a, has_w, stream))
+    return rc;
   if (a.n_heavy > 0) {
     const dim3 grid((unsigned)a.n_heavy), block(256);
     if (a.d % 4 == 0) hipLaunchKernelGGL(k_fixup<4>, grid, block, 0, stream, a);
@@ -521,6 +579,35 @@ int hgnn_gather_reduce_scaled(const float* x, int64_t n_x, int32_t d, const int3
   return run_gather(a, as_stream(stream));
 }
 
+int hgnn_gather_reduce_bf16(const uint16_t* x, int64_t n_x, int32_t d, const int32_t* rowptr,
+                            const int32_t* col, int64_t n_rows, const float* edge_w,
+                            const float* col_w, const float* row_w, int32_t flags,
+                            const int32_t* heavy_rows, const int32_t* heavy_first,
+                            int64_t n_heavy, int64_t n_chunks, int32_t chunk, float* slab,
+                            float* out, int64_t acc_limit, const int32_t* col_hot,
+                            float hot_share, hgnn_stream_t stream) {
+  if (d > 0 && (d % 8 != 0 || d > 1024))
+    return fail(HGNN_E_UNSUPPORTED,
+                "gather_reduce_bf16: d=%d (bf16 rows need d %% 8 == 0 and d <= 1024)", d);
+  if (row_w && (flags & HGNN_MEAN))
+    return fail(HGNN_E_ARG, "gather_reduce_bf16: row_w replaces HGNN_MEAN, not both");
+  if (acc_limit < 0) return fail(HGNN_E_ARG, "gather_reduce_bf16: acc_limit < 0");
+  GatherArgs a{};
+  a.x = x; a.rowptr = rowptr; a.col = col; a.edge_w = edge_w; a.col_w = col_w; a.row_w = row_w;
+  a.heavy_rows = heavy_rows; a.heavy_first = heavy_first; a.slab = slab; a.out = out;
+  a.n_rows = n_rows; a.n_heavy = n_heavy; a.n_items = n_rows + (n_heavy > 0 ? n_chunks : 0);
+  a.d = d; a.chunk = chunk; a.mean = (flags & HGNN_MEAN) ? 1 : 0;
+  a.accumulate = (flags & HGNN_ACCUMULATE) ? 1 : 0;
+  a.acc_limit = acc_limit;
+  a.bf16 = 1;
+  nt_policy(a, n_x, 2);
+  if (hot_policy(n_x * (int64_t)d * 2, col_hot != nullptr, hot_share)) {
+    a.col = col_hot;
+    a.hot = 1;
+  }
+  return run_gather(a, as_stream(stream));
+}
+
 int hgnn_gather_mean_fwd(const float* x_src, int64_t n_src, int32_t d, const int32_t* rowptr,
                          const int32_t* col, int64_t n_dst, const int32_t* heavy_rows,
                          const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
@@ -573,6 +660,28 @@ int hgnn_score_gather2(const float* x, int64_t n_x, const float* rowvec, int32_t
   a.rowvec = rowvec; a.cscale = cscale; a.inv_e = inv_e; a.score = 1;
   a.rowptr2 = rowptr_n; a.col2 = col_n;
   nt_policy(a, n_x);
+  return run_gather(a, as_stream(stream));
+}
+
+int hgnn_score_gather2_bf16(const uint16_t* x, int64_t n_x, const uint16_t* rowvec, int32_t d,
+                            const int32_t* rowptr, const int32_t* col, const int32_t* rowptr_n,
+                            const int32_t* col_n, int64_t n_rows, const float* cscale,
+                            float inv_e, const int32_t* heavy_rows, const int32_t* heavy_first,
+                            int64_t n_heavy, int64_t n_chunks, int32_t chunk, float* slab,
+                            float* out, hgnn_stream_t stream) {
+  if (d > 0 && (d % 8 != 0 || d > 1024))
+    return fail(HGNN_E_UNSUPPORTED,
+                "score_gather2_bf16: d=%d (bf16 rows need d %% 8 == 0 and d <= 1024)", d);
+  if (!rowptr_n && n_rows > 0) return fail(HGNN_E_ARG, "score_gather2_bf16: rowptr_n is null");
+  GatherArgs a{};
+  a.x = x; a.rowptr = rowptr; a.col = col;
+  a.heavy_rows = heavy_rows; a.heavy_first = heavy_first; a.slab = slab; a.out = out;
+  a.n_rows = n_rows; a.n_heavy = n_heavy; a.n_items = n_rows + (n_heavy > 0 ? n_chunks : 0);
+  a.d = d; a.chunk = chunk;
+  a.rowvec = rowvec; a.cscale = cscale; a.inv_e = inv_e; a.score = 1;
+  a.rowptr2 = rowptr_n; a.col2 = col_n;
+  a.bf16 = 1;
+  nt_policy(a, n_x, 2);
   return run_gather(a, as_stream(stream));
 }
 

@@ -107,6 +107,86 @@ struct Vec<1> {
   static __device__ __forceinline__ T shfl_xor(T v, int m) { return __shfl_xor(v, m, 64); }
 };
 
+// W = 8: the fragment of a bf16 source row (16 B = 8 elements per lane) widened to fp32; the
+// fp32 side of such a gather (accumulators, output rows) is two float4 per lane.
+struct float8 {
+  float4 lo, hi;
+};
+template <>
+struct Vec<8> {
+  using T = float8;
+  using H = Vec<4>;
+  static __device__ __forceinline__ T zero() { return T{H::zero(), H::zero()}; }
+  static __device__ __forceinline__ T load(const float* p) { return T{H::load(p), H::load(p + 4)}; }
+  static __device__ __forceinline__ T load_nt(const float* p) {
+    return T{H::load_nt(p), H::load_nt(p + 4)};
+  }
+  static __device__ __forceinline__ void store(float* p, T v) {
+    H::store(p, v.lo);
+    H::store(p + 4, v.hi);
+  }
+  static __device__ __forceinline__ void store_nt(float* p, T v) {
+    H::store_nt(p, v.lo);
+    H::store_nt(p + 4, v.hi);
+  }
+  static __device__ __forceinline__ void fma(T& a, float w, T v) {
+    H::fma(a.lo, w, v.lo);
+    H::fma(a.hi, w, v.hi);
+  }
+  static __device__ __forceinline__ void add(T& a, T v) {
+    H::add(a.lo, v.lo);
+    H::add(a.hi, v.hi);
+  }
+  static __device__ __forceinline__ float dot(T a, T b) {
+    float s = H::dot(a.lo, b.lo);
+    s = fmaf(a.hi.x, b.hi.x, s); s = fmaf(a.hi.y, b.hi.y, s);
+    s = fmaf(a.hi.z, b.hi.z, s); s = fmaf(a.hi.w, b.hi.w, s);
+    return s;
+  }
+  static __device__ __forceinline__ void scale(T& a, float s) {
+    H::scale(a.lo, s);
+    H::scale(a.hi, s);
+  }
+  static __device__ __forceinline__ T shfl_xor(T v, int m) {
+    return T{H::shfl_xor(v.lo, m), H::shfl_xor(v.hi, m)};
+  }
+};
+
+// The source rows of a gather, by element type.  fp32 rows (XT = float) are read as the fragment
+// itself and `widen` is the identity, so those kernels are the code they were.  bf16 rows (XT =
+// uint16_t, W = 8) are read 16 B per lane, stay packed (4 registers per vector) while in flight
+// and are widened where they are summed: a shift or a mask per element, exact.
+template <typename XT, int W>
+struct RowSrc {
+  using V = Vec<W>;
+  using Raw = typename V::T;
+  static __device__ __forceinline__ Raw zero() { return V::zero(); }
+  static __device__ __forceinline__ Raw load(const float* p) { return V::load(p); }
+  static __device__ __forceinline__ Raw load_nt(const float* p) { return V::load_nt(p); }
+  static __device__ __forceinline__ typename V::T widen(Raw r) { return r; }
+};
+template <>
+struct RowSrc<uint16_t, 8> {
+  using Raw = uint4;
+  static __device__ __forceinline__ Raw zero() { return make_uint4(0u, 0u, 0u, 0u); }
+  static __device__ __forceinline__ Raw load(const uint16_t* p) {
+    return *reinterpret_cast<const uint4*>(p);
+  }
+  static __device__ __forceinline__ Raw load_nt(const uint16_t* p) {
+    typedef unsigned int u4 __attribute__((ext_vector_type(4)));
+    const u4 v = __builtin_nontemporal_load(reinterpret_cast<const u4*>(p));
+    return make_uint4(v.x, v.y, v.z, v.w);
+  }
+  // element 2k sits in the low half of word k, element 2k + 1 in its high half
+  static __device__ __forceinline__ float4 widen2(uint32_t a, uint32_t b) {
+    return make_float4(__uint_as_float(a << 16), __uint_as_float(a & 0xffff0000u),
+                       __uint_as_float(b << 16), __uint_as_float(b & 0xffff0000u));
+  }
+  static __device__ __forceinline__ float8 widen(Raw r) {
+    return float8{widen2(r.x, r.y), widen2(r.z, r.w)};
+  }
+};
+
 // Device exclusive scan of int32 counts (n entries) -> out (n+1 entries, out[n] = total).
 // Workspace query with ws == nullptr.
 // Sum over aligned groups of LPR lanes (power of 2), result in every lane of the group.  Within a

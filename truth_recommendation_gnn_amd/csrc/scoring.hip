@@ -29,8 +29,8 @@
 namespace hgnn {
 
 struct ScoreArgs {
-  const float* U;
-  const float* P;
+  const void* U;               // fp32 rows, or bf16 rows in the XT = uint16_t instantiation
+  const void* P;
   const int32_t* rowptr;       // user-grouped CSR of the positive edges
   const int32_t* col;          // post id per position
   const int64_t* neg;          // negative post id per position (user-grouped order) ...
@@ -58,7 +58,12 @@ __device__ __forceinline__ float slot_dot(const typename Vec<W>::T (&a)[VPL],
   float s = 0.f;
 #pragma unroll
   for (int q = 0; q < VPL; ++q) {
-    if constexpr (W == 4) {
+    if constexpr (W == 8) {
+      s = fmaf(a[q].lo.x, b[q].lo.x, s); s = fmaf(a[q].lo.y, b[q].lo.y, s);
+      s = fmaf(a[q].lo.z, b[q].lo.z, s); s = fmaf(a[q].lo.w, b[q].lo.w, s);
+      s = fmaf(a[q].hi.x, b[q].hi.x, s); s = fmaf(a[q].hi.y, b[q].hi.y, s);
+      s = fmaf(a[q].hi.z, b[q].hi.z, s); s = fmaf(a[q].hi.w, b[q].hi.w, s);
+    } else if constexpr (W == 4) {
       s = fmaf(a[q].x, b[q].x, s); s = fmaf(a[q].y, b[q].y, s);
       s = fmaf(a[q].z, b[q].z, s); s = fmaf(a[q].w, b[q].w, s);
     } else {
@@ -68,9 +73,14 @@ __device__ __forceinline__ float slot_dot(const typename Vec<W>::T (&a)[VPL],
   return slot_sum<LPR>(s);
 }
 
-template <int LPR, int VPL, int W, bool NT = false>
+// XT: the element type of U and P (RowSrc).  bf16 rows are read 16 B per lane (W = 8), held packed
+// in the ping-pong sets and widened to fp32 where a step is scored; dU and the loss stay fp32.
+template <int LPR, int VPL, int W, bool NT = false, typename XT = float>
 __global__ void __launch_bounds__(256) k_edge_score(const ScoreArgs a) {
   using V = Vec<W>;
+  using S = RowSrc<XT, W>;
+  const XT* const Ux = static_cast<const XT*>(a.U);
+  const XT* const Px = static_cast<const XT*>(a.P);
   constexpr int NS = 64 / LPR;
   __shared__ float red[2][4];
   // wave index through readfirstlane: u, the row bounds and n are then scalar (wave-uniform to
@@ -92,7 +102,7 @@ __global__ void __launch_bounds__(256) k_edge_score(const ScoreArgs a) {
 #pragma unroll
     for (int q = 0; q < VPL; ++q) {
       const int cc = (q * LPR + sl) * W;
-      uv[q] = cc < d ? V::load(a.U + u * d + cc) : V::zero();
+      uv[q] = cc < d ? S::widen(S::load(Ux + u * d + cc)) : V::zero();
       acc[q] = V::zero();
     }
     for (int64_t base = beg; base < end; base += 64) {
@@ -116,22 +126,28 @@ __global__ void __launch_bounds__(256) k_edge_score(const ScoreArgs a) {
       // is 0 past d, and the dU store is guarded).  Under exec-mask branches the compiler's
       // waitcnt pass could not count the prefetch and waited for it before using the previous
       // step's rows.
-      typename V::T ap[VPL], an[VPL], bp[VPL], bn[VPL];
-      auto load_step = [&](int j, typename V::T (&xp)[VPL], typename V::T (&xn)[VPL]) {
+      typename S::Raw ap[VPL], an[VPL], bp[VPL], bn[VPL];
+      auto load_step = [&](int j, typename S::Raw (&xp)[VPL], typename S::Raw (&xn)[VPL]) {
         const int e = j + slot;
         const int pp = __shfl(pid, e & 63, 64), qq = __shfl(nid, e & 63, 64);
 #pragma unroll
         for (int q = 0; q < VPL; ++q) {
           const int cc = (q * LPR + sl) * W;
           const int ccl = cc < d ? cc : 0;
-          xp[q] = V::load(a.P + (int64_t)pp * d + ccl);
-          if constexpr (NT) xn[q] = V::load_nt(a.P + (int64_t)qq * d + ccl);
-          else xn[q] = V::load(a.P + (int64_t)qq * d + ccl);
+          xp[q] = S::load(Px + (int64_t)pp * d + ccl);
+          if constexpr (NT) xn[q] = S::load_nt(Px + (int64_t)qq * d + ccl);
+          else xn[q] = S::load(Px + (int64_t)qq * d + ccl);
         }
       };
-      auto score_step = [&](int j, const typename V::T (&vp)[VPL],
-                            const typename V::T (&vn)[VPL]) {
+      auto score_step = [&](int j, const typename S::Raw (&rp)[VPL],
+                            const typename S::Raw (&rn)[VPL]) {
         const int e = j + slot;
+        typename V::T vp[VPL], vn[VPL];
+#pragma unroll
+        for (int q = 0; q < VPL; ++q) {
+          vp[q] = S::widen(rp[q]);
+          vn[q] = S::widen(rn[q]);
+        }
         const float sp = slot_dot<LPR, VPL, W>(uv, vp);
         const float sn = slot_dot<LPR, VPL, W>(uv, vn);
         const float tp = exp_neg_abs(sp), tn = exp_neg_abs(sn);
@@ -301,14 +317,14 @@ __global__ void __launch_bounds__(1024) k_loss_one(const float* part, int64_t n_
 // few enough partials for one block to sum them faster than two launches
 constexpr int64_t kLossOneMax = 65536;
 
-template <int LPR, int VPL, int W>
+template <int LPR, int VPL, int W, typename XT = float>
 static int launch_score(const ScoreArgs& a, int64_t nblocks, hipStream_t stream) {
   if (a.nt_neg)   // the cache policy as its own instantiation: the default one is unchanged
-    hipLaunchKernelGGL((k_edge_score<LPR, VPL, W, true>), dim3((unsigned)nblocks), dim3(256), 0,
-                       stream, a);
+    hipLaunchKernelGGL((k_edge_score<LPR, VPL, W, true, XT>), dim3((unsigned)nblocks), dim3(256),
+                       0, stream, a);
   else
-    hipLaunchKernelGGL((k_edge_score<LPR, VPL, W>), dim3((unsigned)nblocks), dim3(256), 0,
-                     stream, a);
+    hipLaunchKernelGGL((k_edge_score<LPR, VPL, W, false, XT>), dim3((unsigned)nblocks),
+                       dim3(256), 0, stream, a);
   return check_launch("k_edge_score");
 }
 
@@ -323,13 +339,14 @@ int64_t hgnn_edge_score_parts(int64_t n_users) {
   return (int64_t)align_up((size_t)(2 * cdiv(n_users, 4)), 4) + 4 * kRedBlocks;
 }
 
-static int edge_score_fwd(const float* U, const float* P, int32_t d, int64_t n_users,
+// `bf16`: U and P hold bf16 rows (hgnn_edge_score_fwd_bf16)
+static int edge_score_fwd(const void* U, const void* P, int32_t d, int64_t n_users,
                           int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
                           const int64_t* neg_u_order, const int32_t* neg32,
                           const uint64_t* neg_seed, const int32_t* to_post_pos, int64_t n_edges, const float* cscale,
                           float* dU, float* hpos, int32_t* neg_key, int32_t* neg_user,
                           float* neg_w, float* part, float* loss, int32_t* err,
-                          hgnn_stream_t stream_) {
+                          hgnn_stream_t stream_, bool bf16 = false) {
   hipStream_t stream = as_stream(stream_);
   if (d < 1 || n_users < 0 || n_posts < 0 || n_edges < 0)
     return fail(HGNN_E_ARG, "edge_score: bad sizes");
@@ -344,13 +361,20 @@ static int edge_score_fwd(const float* U, const float* P, int32_t d, int64_t n_u
   a.to_post_pos = to_post_pos; a.cscale = cscale; a.dU = dU; a.hpos = hpos; a.neg_key = neg_key;
   a.neg_u = neg_user; a.neg_w = neg_w; a.part = part; a.err = err; a.n_users = n_users;
   a.n_posts = n_posts; a.inv_e = n_edges > 0 ? 1.f / (float)n_edges : 0.f; a.d = d;
-  a.nt_neg = n_posts * d * 4 >= (int64_t(256) << 20) ? 1 : 0;
+  a.nt_neg = n_posts * d * (bf16 ? 2 : 4) >= (int64_t(256) << 20) ? 1 : 0;   // the table's bytes
   const int64_t nb = cdiv(n_users, 4);   // blocks of 4 user-waves
   int rc = HGNN_OK;
   if (nb > 0) {
     // one 4..16-edge step per iteration, next step's loads pipelined (an unrolled 2-step body
     // measured slower: users average ~20 edges, so wider steps waste the tail)
-    if (d % 4 == 0 && d <= 64) rc = launch_score<16, 1, 4>(a, nb, stream);
+    if (bf16) {   // 16 B = 8 elements per lane: d = 128 is 16 lanes per row, 4 edges per step
+      using B = uint16_t;
+      if (d <= 64) rc = launch_score<8, 1, 8, B>(a, nb, stream);
+      else if (d <= 128) rc = launch_score<16, 1, 8, B>(a, nb, stream);
+      else if (d <= 256) rc = launch_score<32, 1, 8, B>(a, nb, stream);
+      else rc = launch_score<64, 1, 8, B>(a, nb, stream);
+    }
+    else if (d % 4 == 0 && d <= 64) rc = launch_score<16, 1, 4>(a, nb, stream);
     else if (d % 4 == 0 && d <= 128) rc = launch_score<32, 1, 4>(a, nb, stream);
     else if (d % 4 == 0 && d <= 256) rc = launch_score<64, 1, 4>(a, nb, stream);
     else if (d <= 64) rc = launch_score<64, 1, 1>(a, nb, stream);
@@ -405,6 +429,27 @@ int hgnn_edge_score_fwd_draw(const float* U, const float* P, int32_t d, int64_t 
   return edge_score_fwd(U, P, d, n_users, n_posts, rowptr_u, col_u, nullptr, nullptr, d_seed,
                         nullptr, n_edges, cscale, dU, nullptr, nullptr, nullptr, nullptr, part,
                         loss, err, stream);
+}
+
+int hgnn_edge_score_fwd_bf16(const uint16_t* U, const uint16_t* P, int32_t d, int64_t n_users,
+                             int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
+                             const int64_t* neg_i64, const int32_t* neg_i32,
+                             const uint64_t* d_seed, int64_t n_edges, const float* cscale,
+                             float* dU, float* part, float* loss, int32_t* err,
+                             hgnn_stream_t stream) {
+  if (d > 0 && (d % 8 != 0 || d > 512))
+    return fail(HGNN_E_UNSUPPORTED,
+                "edge_score_fwd_bf16: d=%d (bf16 rows need d %% 8 == 0 and d <= 512)", d);
+  const int given = (neg_i64 != nullptr) + (neg_i32 != nullptr) + (d_seed != nullptr);
+  if (given > 1 || (n_edges > 0 && given != 1))
+    return fail(HGNN_E_ARG, "edge_score_fwd_bf16: the negatives come in exactly one form "
+                            "(int64, int32 or a seed)");
+  if (d_seed && (n_posts < 1 || n_posts >= (int64_t(1) << 31) - 1))
+    return fail(HGNN_E_ARG, "edge_score_fwd_bf16: n_posts=%lld out of range for drawn negatives",
+                (long long)n_posts);
+  return edge_score_fwd(U, P, d, n_users, n_posts, rowptr_u, col_u, neg_i64, neg_i32, d_seed,
+                        nullptr, n_edges, cscale, dU, nullptr, nullptr, nullptr, nullptr, part,
+                        loss, err, stream, true);
 }
 
 // Uniform draws in [0, hi): out[i] = hi * (splitmix64(seed + i * golden) >> 32) >> 32 (Lemire's

@@ -32,6 +32,32 @@ def _check_f32(t: torch.Tensor, what: str) -> torch.Tensor:
     return t.contiguous()
 
 
+# ----------------------------------------------------------------------------- row storage
+# How the forward gathers and the link loss store the rows they read once per edge from a layer
+# output.  "fp32" (the default): the tables themselves, the fp32 parity path.  "bf16" (opt-in):
+# a bf16 copy of each such table (``rows_to_bf16``, round to nearest even), half the row bytes;
+# every result is then what the fp32 path gives on R(T) = T.to(bfloat16).float(), gradients pass
+# straight through R, and everything that is not a gathered row stays fp32.
+# Read from HGNN_ROW_DTYPE at import, as HGNN_HOT_ROWS / HGNN_STATIC_AGG are; a LayerSpec, the
+# model constructors and the loss take a ``row_dtype`` of their own, None meaning this value at
+# call time.
+ROW_DTYPES = ("fp32", "bf16")
+
+
+def _row_dtype_value(v: str, what: str) -> str:
+    if v not in ROW_DTYPES:
+        raise ValueError(f"{what}={v!r}: the row storage is 'fp32' or 'bf16'")
+    return v
+
+
+ROW_DTYPE = _row_dtype_value(os.environ.get("HGNN_ROW_DTYPE", "fp32"), "HGNN_ROW_DTYPE")
+
+
+def resolve_row_dtype(row_dtype: Optional[str]) -> str:
+    """``row_dtype`` itself, or the module's ``ROW_DTYPE`` (as it is now) for None."""
+    return _row_dtype_value(ROW_DTYPE if row_dtype is None else row_dtype, "row_dtype")
+
+
 # ----------------------------------------------------------------------------- kernel timing
 class KernelTimer:
     """Records HIP events around every kernel call this module makes (on the current stream,
@@ -88,16 +114,45 @@ class _timed:
                                    int(self.flops)))
 
 
-def gather_bytes(n_edges: int, n_rows: int, d: int, weighted: bool) -> int:
+def gather_bytes(n_edges: int, n_rows: int, d: int, weighted: bool,
+                 row_bytes: Optional[int] = None) -> int:
     """Algorithmic HBM bytes of one K1/K2 launch: per edge a 4-B index and one
-    4*d-B source row (+4 B weight for K2), rowptr, and the output rows."""
-    return 4 * n_edges * (1 + d + (1 if weighted else 0)) + 4 * (n_rows + 1) + 4 * n_rows * d
+    source row of ``row_bytes`` (4*d for fp32 rows, the default; 2*d for bf16 rows) (+4 B weight
+    for K2), rowptr, and the fp32 output rows."""
+    rb = 4 * d if row_bytes is None else int(row_bytes)
+    return (n_edges * (4 + rb + (4 if weighted else 0)) + 4 * (n_rows + 1) + 4 * n_rows * d)
 
 
-def gather_compulsory_bytes(n_edges: int, n_rows: int, n_src: int, d: int, weighted: bool) -> int:
+def gather_compulsory_bytes(n_edges: int, n_rows: int, n_src: int, d: int, weighted: bool,
+                            row_bytes: Optional[int] = None) -> int:
     """As gather_bytes with each source row read once: min(E, N_src) rows instead of E."""
-    return (4 * n_edges * (1 + (1 if weighted else 0)) + 4 * min(n_edges, n_src) * d
+    rb = 4 * d if row_bytes is None else int(row_bytes)
+    return (4 * n_edges * (1 + (1 if weighted else 0)) + min(n_edges, n_src) * rb
             + 4 * (n_rows + 1) + 4 * n_rows * d)
+
+
+def _row_bytes(x: torch.Tensor) -> int:
+    return int(x.shape[1]) * x.element_size()
+
+
+def rows_to_bf16(x: torch.Tensor) -> torch.Tensor:
+    """The bf16 copy of an fp32 tensor (``hgnn_rows_to_bf16``): round to nearest even, bitwise
+    ``x.to(torch.bfloat16)``.  One streaming pass; the row mode's shadow tables."""
+    x = _check_f32(x, "rows_to_bf16")
+    dev = N.require_device(x)
+    out = torch.empty(x.shape, dtype=torch.bfloat16, device=dev)
+    name = f"rows_to_bf16[{x.shape[0]}]x{x.shape[1]}" if x.dim() == 2 else "rows_to_bf16"
+    with _timed(name, 6 * x.numel()):
+        N.check(N.lib().hgnn_rows_to_bf16(N.ptr(x), x.numel(), N.ptr(out), N.stream_ptr(dev)),
+                "hgnn_rows_to_bf16")
+    return out
+
+
+def _check_table(t: torch.Tensor, what: str) -> torch.Tensor:
+    """A gather's source table: fp32, or the bf16 rows of the row mode."""
+    if t.dtype == torch.bfloat16:
+        return t.contiguous()
+    return _check_f32(t, what)
 
 
 # ----------------------------------------------------------------------------- raw kernel calls
@@ -137,6 +192,13 @@ def _gather_blocked(x, passes, row_w, edge_w, out, accumulate, name, nbytes, cby
             slab = (torch.empty(p.n_chunks * d, dtype=torch.float32, device=dev)
                     if p.n_heavy else None)
             flags = N.HGNN_ACCUMULATE if (accumulate or b > 0) else 0
+            if x.dtype == torch.bfloat16:
+                N.check(lib.hgnn_gather_reduce_bf16(
+                    N.ptr(x), x.shape[0], d, N.ptr(g.rowptr), N.ptr(g.col), g.n_rows,
+                    N.ptr(edge_w), None, N.ptr(row_w), flags, N.ptr(p.heavy_rows),
+                    N.ptr(p.heavy_first), p.n_heavy, p.n_chunks, p.chunk, N.ptr(slab), N.ptr(out),
+                    0, None, 0.0, s), "hgnn_gather_reduce_bf16")
+                continue
             N.check(lib.hgnn_gather_reduce_scaled(
                 N.ptr(x), x.shape[0], d, N.ptr(g.rowptr), N.ptr(g.col), g.n_rows, N.ptr(edge_w),
                 None, N.ptr(row_w), flags, N.ptr(p.heavy_rows), N.ptr(p.heavy_first), p.n_heavy,
@@ -292,8 +354,12 @@ def gather_mean(x_src: torch.Tensor, csr: RelationCSR,
     the keeping off."""
     if static and out is not None:
         raise ValueError("gather_mean: a static aggregate is never accumulated into (out=)")
+    if static and x_src.dtype == torch.bfloat16:
+        raise ValueError("gather_mean: a static model input is gathered once and kept as fp32 "
+                         "rows; bf16 rows are for tables that change every step (static=True "
+                         "with a bfloat16 table)")
     given = x_src
-    x_src = _check_f32(x_src, "gather_mean")
+    x_src = _check_table(x_src, "gather_mean")
     dev = N.require_device(x_src, csr.fwd.rowptr)
     if x_src.shape[0] != csr.n_src:
         raise ValueError(f"x_src has {x_src.shape[0]} rows, relation expects {csr.n_src}")
@@ -308,10 +374,11 @@ def gather_mean(x_src: torch.Tensor, csr: RelationCSR,
     if B > 1:
         passes, _ = csr.blocks("fwd", B)
         E = csr.num_edges
+        rb = _row_bytes(x_src)
         _gather_blocked(x_src, passes, csr.inv_deg, None, out, acc,
                         f"gather_fwd[{csr.n_dst}<-{csr.n_src}]x{d}",
-                        gather_bytes(E, csr.n_dst, d, False),
-                        gather_compulsory_bytes(E, csr.n_dst, csr.n_src, d, False))
+                        gather_bytes(E, csr.n_dst, d, False, rb),
+                        gather_compulsory_bytes(E, csr.n_dst, csr.n_src, d, False, rb))
         return out
     _gather(x_src, csr.fwd, None, csr_mean=True, out=out, accumulate=acc,
             hot=csr.hot_cols("fwd", _table_bytes(x_src)))
@@ -399,8 +466,18 @@ def _gather(x, grouped, col_w, csr_mean, out, accumulate, edge_w=None, kind=None
     kind = kind or ("fwd" if csr_mean else "bwd")   # "wfwd": weighted forward (parallel.py)
     name = f"gather_{kind}[{grouped.n_rows}<-{x.shape[0]}]x{d}"   # [dst rows <- src rows] x d
     E = int(grouped.col.numel())
-    with _timed(name, gather_bytes(E, grouped.n_rows, d, weighted),
-                gather_compulsory_bytes(E, grouped.n_rows, int(x.shape[0]), d, weighted)):
+    rb = _row_bytes(x)
+    with _timed(name, gather_bytes(E, grouped.n_rows, d, weighted, rb),
+                gather_compulsory_bytes(E, grouped.n_rows, int(x.shape[0]), d, weighted, rb)):
+        if x.dtype == torch.bfloat16:
+            N.check(N.lib().hgnn_gather_reduce_bf16(
+                N.ptr(x), x.shape[0], d, N.ptr(grouped.rowptr), N.ptr(grouped.col),
+                grouped.n_rows, N.ptr(edge_w), N.ptr(col_w), None, flags, N.ptr(p.heavy_rows),
+                N.ptr(p.heavy_first), p.n_heavy, p.n_chunks, p.chunk, N.ptr(slab), N.ptr(out),
+                0, N.ptr(hot.col) if hot is not None else None,
+                hot.share if hot is not None else 0.0, N.stream_ptr(dev)),
+                "hgnn_gather_reduce_bf16")
+            return
         if hot is not None:
             N.check(N.lib().hgnn_gather_reduce_hot(
                 N.ptr(x), x.shape[0], d, N.ptr(grouped.rowptr), N.ptr(grouped.col),
@@ -447,9 +524,17 @@ def _score_gather2(U, P, pos, negs, cscale, inv_e, out):
     if p.n_heavy:
         slab = torch.empty(p.n_chunks * d, dtype=torch.float32, device=dev)
     E = int(pos.col.numel()) + int(negs.col.numel())
-    nb = gather_bytes(E, n, d, False) + 4 * (n + 1) + 4 * n * d
-    cb = gather_compulsory_bytes(E, n, int(U.shape[0]), d, False) + 4 * (n + 1) + 4 * n * d
+    rb = _row_bytes(U)      # U's rows per edge and P's own row per output row
+    nb = gather_bytes(E, n, d, False, rb) + 4 * (n + 1) + n * rb
+    cb = gather_compulsory_bytes(E, n, int(U.shape[0]), d, False, rb) + 4 * (n + 1) + n * rb
     with _timed(f"score_gather[{n}<-{U.shape[0]}]x{d}", nb, cb):
+        if U.dtype == torch.bfloat16:
+            N.check(N.lib().hgnn_score_gather2_bf16(
+                N.ptr(U), U.shape[0], N.ptr(P), d, N.ptr(pos.rowptr), N.ptr(pos.col),
+                N.ptr(negs.rowptr), N.ptr(negs.col), n, N.ptr(cscale), inv_e,
+                N.ptr(p.heavy_rows), N.ptr(p.heavy_first), p.n_heavy, p.n_chunks, p.chunk,
+                N.ptr(slab), N.ptr(out), N.stream_ptr(dev)), "hgnn_score_gather2_bf16")
+            return
         N.check(N.lib().hgnn_score_gather2(
             N.ptr(U), U.shape[0], N.ptr(P), d, N.ptr(pos.rowptr), N.ptr(pos.col),
             N.ptr(negs.rowptr), N.ptr(negs.col), n, N.ptr(cscale), inv_e, N.ptr(p.heavy_rows),
@@ -980,6 +1065,21 @@ def use_pre_projection(x_src: torch.Tensor, x_dst: torch.Tensor, hidden: int,
 class LayerSpec:
     types: Tuple[str, ...]                       # order of node-feature inputs
     groups: Tuple[DstGroup, ...]
+    # storage of the rows the layer's forward gathers: "fp32", "bf16", or None for ops.ROW_DTYPE
+    # at call time (see ``_rounds``)
+    row_dtype: Optional[str] = None
+
+
+def _rounds(g: DstGroup, i: int, width: int) -> bool:
+    """bf16 row mode: whether relation i of the group gathers the bf16 copy of its table (of
+    ``width`` columns: the source table, or the projected rows of a pre-projected relation).
+    Only a full-table group's relations do (a sampled block — ``n_root`` / ``root_src`` — keeps
+    fp32 rows), never one whose table the caller declared static (a model input is gathered once
+    and kept, whatever HGNN_STATIC_AGG says), and only at a width that is a multiple of 8."""
+    if g.n_root is not None or g.root_src is not None or width % 8 != 0:
+        return False
+    pre = i < len(g.pre) and g.pre[i]
+    return bool(pre or not (i < len(g.static) and g.static[i]))
 
 
 class _Lanes:
@@ -1031,15 +1131,37 @@ class _HeteroLayer(torch.autograd.Function):
         ng = len(spec.groups)
         outs, aggrs_by_g, masks = [None] * ng, [None] * ng, [None] * ng
         dev = flat[0].device
+        # bf16 row mode: one bf16 copy per distinct source table some relation of the layer
+        # gathers (``_rounds``), cast here on the caller's stream before the lanes fork and held
+        # until the forward returns.  Nothing is saved from them: the backward is the fp32 one,
+        # evaluated at the aggregates computed from the rounded rows.
+        bf16 = resolve_row_dtype(spec.row_dtype) == "bf16"
+        shadow: Dict[str, torch.Tensor] = {}
+        if bf16:
+            for g in spec.groups:
+                for i, (src, _) in enumerate(g.rels):
+                    if (src not in shadow and not (i < len(g.pre) and g.pre[i])
+                            and _rounds(g, i, int(xs[src].shape[1]))):
+                        shadow[src] = rows_to_bf16(xs[src])
+
+        def k1(g, i, src, csr):
+            if src in shadow and _rounds(g, i, int(xs[src].shape[1])):
+                return gather_mean(shadow[src], csr)
+            return gather_mean(xs[src], csr, static=_is_static(g, i), name=f"{src}->{g.dst}")
+
         lanes = _Lanes(dev, ng)
         many = None
         if lanes.side is None and not any(any(g.pre) for g in spec.groups):
-            # every relation's K1 of the layer in one launch (sampled blocks; gather_mean_many
-            # falls back to one launch each where they do not qualify)
-            many = iter(gather_mean_many(
-                [(xs[src], csr) for g in spec.groups for src, csr in g.rels],
-                static=[_is_static(g, i) for g in spec.groups for i in range(len(g.rels))],
-                names=[f"{src}->{g.dst}" for g in spec.groups for src, _ in g.rels]))
+            if shadow:
+                many = iter([k1(g, i, src, csr) for g in spec.groups
+                             for i, (src, csr) in enumerate(g.rels)])
+            else:
+                # every relation's K1 of the layer in one launch (sampled blocks;
+                # gather_mean_many falls back to one launch each where they do not qualify)
+                many = iter(gather_mean_many(
+                    [(xs[src], csr) for g in spec.groups for src, csr in g.rels],
+                    static=[_is_static(g, i) for g in spec.groups for i in range(len(g.rels))],
+                    names=[f"{src}->{g.dst}" for g in spec.groups for src, _ in g.rels]))
         if many is not None:
             # and every destination type's K3 in one native call (the split path's column blocks
             # one launch for both types, hgnn_linear_fwd_multi)
@@ -1065,11 +1187,13 @@ class _HeteroLayer(torch.autograd.Function):
                     for i, ((src, csr), pre, (o, k)) in enumerate(zip(g.rels, g.pre, cols)):
                         if pre:
                             P = linear_fwd([xs[src]], w[:, o:o + k].contiguous(), None, False)
+                            if bf16 and _rounds(g, i, int(P.shape[1])):
+                                P = rows_to_bf16(P)    # rounded after the projection: the
+                                                       # table the gather reads
                             add = gather_mean(P, csr, out=add)
                             del P
                         else:
-                            aggrs.append(gather_mean(xs[src], csr, static=_is_static(g, i),
-                                                     name=f"{src}->{g.dst}"))
+                            aggrs.append(k1(g, i, src, csr))
                     segs = aggrs + ([_root(g, xs)] if g.root else [])
                     mk = relu_mask_for(_root(g, xs).shape[0], int(w.shape[0]), g.relu, dev,
                                        sum(int(t.shape[1]) for t in segs))
@@ -1078,9 +1202,7 @@ class _HeteroLayer(torch.autograd.Function):
                                    mask_out=mk)
                     del add
                 else:
-                    aggrs = [gather_mean(xs[src], csr, static=_is_static(g, i),
-                                         name=f"{src}->{g.dst}")
-                             for i, (src, csr) in enumerate(g.rels)]
+                    aggrs = [k1(g, i, src, csr) for i, (src, csr) in enumerate(g.rels)]
                     segs = aggrs + ([_root(g, xs)] if g.root else [])
                     mk = relu_mask_for(segs[0].shape[0], int(w.shape[0]), g.relu, dev,
                                        sum(int(t.shape[1]) for t in segs))
@@ -1089,6 +1211,7 @@ class _HeteroLayer(torch.autograd.Function):
             lanes.escape(gi, y, mk, *aggrs)
             outs[gi], aggrs_by_g[gi], masks[gi] = y, aggrs, mk
         lanes.join()
+        shadow.clear()
         aggrs_all = [a for aggrs in aggrs_by_g for a in aggrs]
         ctx.spec = spec
         ctx.masks = masks          # ReLU bits of each output (None where there is no bit form)
@@ -1504,9 +1627,23 @@ def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total:
     ``p_chunks`` (the sharded step): [(lo, hi, ready_fn)] — the post table arrives in row blocks
     (parallel.DistEnv.broadcast_slices_async); dP's rows [lo, hi) need only those rows of P, so
     the dP gather runs block by block as each lands (ready_fn: a stream wait), and the scoring
-    pass, which reads all of P, after the last."""
-    U = _check_f32(U, "edge_bce_loss user_emb")
-    P = _check_f32(P, "edge_bce_loss post_emb")
+    pass, which reads all of P, after the last.
+
+    ``U`` and ``P`` are fp32 tables, or both their bf16 copies (the bf16 row mode: both passes
+    then read the bf16 rows, so the score <R(U[u]), R(P[p])> is one number in the scoring pass
+    and in the dP gather; loss, dU and dP stay fp32).  The sharded step's arguments (``ready``,
+    ``on_dP``, ``p_chunks``) are for fp32 rows only."""
+    bf16 = U.dtype == torch.bfloat16
+    if bf16:
+        if P.dtype != torch.bfloat16:
+            raise TypeError("edge_bce_loss: bf16 rows need both tables in bfloat16")
+        if ready is not None or on_dP is not None or p_chunks is not None:
+            raise ValueError("edge_bce_loss: bf16 rows do not combine with ready / on_dP / "
+                             "p_chunks (the sharded step runs on fp32 rows)")
+        U, P = U.contiguous(), P.contiguous()
+    else:
+        U = _check_f32(U, "edge_bce_loss user_emb")
+        P = _check_f32(P, "edge_bce_loss post_emb")
     draw = neg_u_order if isinstance(neg_u_order, NegativeDraw) else None
     dev = N.require_device(U, P, draw.seed if draw is not None else neg_u_order)
     lib, s = N.lib(), N.stream_ptr(dev)
@@ -1519,10 +1656,11 @@ def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total:
         # pointer whenever the global edge count is non-zero)
         if ready is not None:
             ready()
-        return (torch.zeros((), dtype=torch.float32, device=dev), torch.zeros_like(U),
-                torch.zeros_like(P))
+        return (torch.zeros((), dtype=torch.float32, device=dev),
+                torch.zeros(U.shape, dtype=torch.float32, device=dev),
+                torch.zeros(P.shape, dtype=torch.float32, device=dev))
     ub, pf = csr.bwd, csr.fwd
-    dU = torch.empty_like(U)
+    dU = torch.empty(U.shape, dtype=torch.float32, device=dev)
     part = torch.empty(int(lib.hgnn_edge_score_parts(nu)), dtype=torch.float32, device=dev)
     loss = torch.empty((), dtype=torch.float32, device=dev)
     # err[0]: zeroed and counted by the scoring pass, err[1] by the int64 negatives sort
@@ -1537,7 +1675,7 @@ def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total:
         neg = None   # drawn again where read (the sort's first pass, the scoring pass)
     else:
         neg = neg_u_order.contiguous() if neg32 else neg_u_order.to(torch.int64).contiguous()
-    dP = torch.empty_like(P)
+    dP = torch.empty(P.shape, dtype=torch.float32, device=dev)
     # dP chain (side stream under HGNN_STREAMS=1): sort the negatives (post, user) by post,
     # then the two dP gathers, each edge's weight recomputed from <U[u], P[post]>
     # (hgnn_score_gather); pass A (loss + dU) needs none of it.
@@ -1576,8 +1714,17 @@ def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total:
         ready()                                 # all of P, for the scoring pass
     # (The scoring pass takes no col_hot: with the positives' cold rows read nt it measured
     # 29-33 ms against 25.4 at cfg4 for every H tried)
-    with _timed(f"edge_score_d{d}", 4 * E * (2 * d + 1 + 2) + 8 * nu * d):
-        if draw is not None:
+    rb = _row_bytes(U)     # per edge two post rows, per user its own row in and a dU row out
+    with _timed(f"edge_score_d{d}", E * (2 * rb + 12) + nu * (rb + 4 * d)):
+        if bf16:
+            N.check(lib.hgnn_edge_score_fwd_bf16(
+                N.ptr(U), N.ptr(P), d, nu, np_, N.ptr(ub.rowptr), N.ptr(ub.col),
+                N.ptr(neg) if draw is None and not neg32 else None,
+                N.ptr(neg) if draw is None and neg32 else None,
+                N.ptr(draw.seed) if draw is not None else None, n_total, N.ptr(c), N.ptr(dU),
+                N.ptr(part), N.ptr(loss), N.ptr(err if check else None), s),
+                "hgnn_edge_score_fwd_bf16")
+        elif draw is not None:
             N.check(lib.hgnn_edge_score_fwd_draw(
                 N.ptr(U), N.ptr(P), d, nu, np_, N.ptr(ub.rowptr), N.ptr(ub.col),
                 N.ptr(draw.seed), n_total, N.ptr(c), N.ptr(dU), N.ptr(part), N.ptr(loss),
@@ -1612,7 +1759,11 @@ class _EdgeBCELoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total: int,
-                ready=None, presorted=None):
+                ready=None, presorted=None, bf16: bool = False):
+        if bf16:
+            # bf16 row mode: both passes read the bf16 copies, and those (half the bytes) are
+            # what stays saved for the retained-graph recompute instead of U and P
+            U, P = rows_to_bf16(U), rows_to_bf16(P)
         loss, dU, dP = _edge_bce(U, P, csr, neg_u_order, cscale, check, n_total, ready,
                                  presorted=presorted)
         ctx.grads = (dU, dP)
@@ -1636,7 +1787,7 @@ class _EdgeBCELoss(torch.autograd.Function):
             for t in (dU, dP):   # in place; a no-op launch for loss.backward()'s gradient of 1
                 N.check(lib.hgnn_scale_unless_one(N.ptr(t), t.numel(), N.ptr(g), s),
                         "hgnn_scale_unless_one")
-        return dU, dP, None, None, None, None, None, None, None
+        return dU, dP, None, None, None, None, None, None, None, None
 
 
 # A tensor carrying this attribute (set True) is a gradient of exactly 1 that nobody writes:
@@ -1658,7 +1809,8 @@ def edge_bce_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: tor
                   neg_order: str = "edge", check: bool = True,
                   n_edges_total: Optional[int] = None,
                   cscale: Optional[torch.Tensor] = None, ready=None,
-                  presorted: Optional["PresortedNegatives"] = None) -> torch.Tensor:
+                  presorted: Optional["PresortedNegatives"] = None,
+                  row_dtype: Optional[str] = None) -> torch.Tensor:
     """Fused HIP version of :func:`link_loss` (same value, same gradients).
 
     ``neg_order='edge'``: ``neg_p[e]`` is the negative of COO edge e (the reference's layout);
@@ -1669,7 +1821,19 @@ def edge_bce_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: tor
     called once the negatives sort is enqueued and before any kernel reads ``post_emb`` (the
     sharded path's post-table all-gather finishes under the sort).  ``presorted``: the grouping
     of these negatives from :func:`presort_negatives`, done ahead (e.g. on a side stream under the
-    forward; the caller orders the streams)."""
+    forward; the caller orders the streams).
+
+    ``row_dtype``: "fp32", "bf16" or None for ``ROW_DTYPE``.  With "bf16" both passes read bf16
+    copies of the two tables (``_edge_bce``); the gradients pass straight through the rounding.
+    A width that is no multiple of 8 keeps fp32 rows, and so does the sharded path (``ready``)
+    under ``ROW_DTYPE`` — asking for "bf16" explicitly together with ``ready`` is an error."""
+    bf16 = resolve_row_dtype(row_dtype) == "bf16"
+    if bf16 and ready is not None:
+        if row_dtype is not None:
+            raise ValueError("edge_bce_loss: row_dtype='bf16' does not combine with ready (the "
+                             "sharded step runs on fp32 rows)")
+        bf16 = False
+    bf16 = bf16 and user_emb.shape[1] % 8 == 0
     csr = relation_csr_for_loss(pos_edges, user_emb.shape[0], post_emb.shape[0])
     if neg_p.shape[0] != csr.num_edges:
         raise ValueError("one negative per positive edge is required (train_gnn.py:272)")
@@ -1679,6 +1843,11 @@ def edge_bce_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: tor
     n_total = csr.num_edges if n_edges_total is None else int(n_edges_total)
     if presorted is not None:
         presorted.check_draws(neg_p, neg_order, "edge_bce_loss")
+    if bf16:
+        _check_f32(user_emb, "edge_bce_loss user_emb")
+        _check_f32(post_emb, "edge_bce_loss post_emb")
+        return _EdgeBCELoss.apply(user_emb, post_emb, csr, neg_u, cscale, check, n_total, ready,
+                                  presorted, True)
     return _EdgeBCELoss.apply(user_emb, post_emb, csr, neg_u, cscale, check, n_total, ready,
                               presorted)
 
@@ -1686,11 +1855,20 @@ def edge_bce_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: tor
 def edge_bce_loss_raw(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: torch.Tensor,
                       neg_p: torch.Tensor, n_edges_total: int, cscale: torch.Tensor,
                       neg_order: str = "user", ready=None, on_dP=None, p_chunks=None,
-                      presorted: Optional[PresortedNegatives] = None):
+                      presorted: Optional[PresortedNegatives] = None, row_dtype: str = "fp32"):
     """:func:`edge_bce_loss` outside autograd: (loss, dL/dU, dL/dP) from the same kernels, for
     callers that run their own backward schedule (``parallel.UserShard.step``; ``on_dP``,
     ``p_chunks``: see ``_edge_bce``; ``presorted``: from :func:`presort_negatives` on the same
-    edges and draws)."""
+    edges and draws).  ``row_dtype`` is "fp32" unless asked otherwise (never ``ROW_DTYPE``:
+    the sharded step stays on fp32 rows); "bf16" casts the two tables and runs both passes on the
+    copies, and is an error together with ``p_chunks``, ``ready`` or ``on_dP``."""
+    if _row_dtype_value(row_dtype, "row_dtype") == "bf16":
+        if ready is not None or on_dP is not None or p_chunks is not None:
+            raise ValueError("edge_bce_loss_raw: row_dtype='bf16' does not combine with "
+                             "p_chunks / ready / on_dP (the sharded step runs on fp32 rows)")
+        if user_emb.shape[1] % 8 == 0:
+            user_emb = rows_to_bf16(_check_f32(user_emb, "edge_bce_loss_raw user_emb"))
+            post_emb = rows_to_bf16(_check_f32(post_emb, "edge_bce_loss_raw post_emb"))
     csr = relation_csr_for_loss(pos_edges, user_emb.shape[0], post_emb.shape[0])
     neg_u = _negatives_user_order(csr, neg_p, neg_order)
     if presorted is not None:
@@ -1771,25 +1949,36 @@ def sample_negatives(pos_edges: torch.Tensor, num_posts: int,
 # multi-GPU path in parallel.py composes them around RCCL collectives).
 class _GatherMean(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x_src, csr: RelationCSR):
+    def forward(ctx, x_src, csr: RelationCSR, bf16: bool = False):
         ctx.csr = csr
+        if bf16:     # the shadow lives for this gather only; K2 below is the fp32 one
+            return gather_mean(rows_to_bf16(x_src), csr)
         return gather_mean(x_src, csr)
 
     @staticmethod
     def backward(ctx, g):
         await_pending(g)     # the halo exchange's adjoint may still be in flight (parallel.py)
         if not ctx.needs_input_grad[0]:
-            return None, None
+            return None, None, None
         if ctx.csr.num_edges == 0:
             # a zero gradient, not None: a rank holding no edge of this relation still has to
             # reach the collective adjoints upstream (parallel.py's halo exchange)
-            return g.new_zeros(ctx.csr.n_src, g.shape[1]), None
-        return scatter_mean_bwd(g.contiguous(), ctx.csr), None
+            return g.new_zeros(ctx.csr.n_src, g.shape[1]), None, None
+        return scatter_mean_bwd(g.contiguous(), ctx.csr), None, None
 
 
-def mean_gather(x_src: torch.Tensor, csr: RelationCSR) -> torch.Tensor:
-    """Differentiable K1 (forward) / K2 (backward) mean aggregation."""
-    return _GatherMean.apply(x_src, csr)
+def mean_gather(x_src: torch.Tensor, csr: RelationCSR,
+                row_dtype: Optional[str] = None) -> torch.Tensor:
+    """Differentiable K1 (forward) / K2 (backward) mean aggregation.  ``row_dtype="bf16"``: the
+    forward gathers the bf16 copy of ``x_src`` (a width that is no multiple of 8 keeps fp32
+    rows); the backward is the same fp32 K2 either way, the gradient passing straight through the
+    rounding.  None is "fp32" whatever ``ROW_DTYPE`` says: this is the composable op of the
+    sharded path (parallel.py), which stays on fp32 rows."""
+    bf16 = (row_dtype is not None and _row_dtype_value(row_dtype, "row_dtype") == "bf16"
+            and x_src.dim() == 2 and x_src.shape[1] % 8 == 0)
+    if not bf16:
+        return _GatherMean.apply(x_src, csr)
+    return _GatherMean.apply(x_src, csr, True)
 
 
 # Gradients still being produced by an in-flight collective (parallel.py issues the adjoint of
