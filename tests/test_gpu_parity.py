@@ -197,7 +197,7 @@ def test_gather_is_deterministic_bitwise():
                                   ([16, 48, 64], 64), ([32, 96], 64), ([48, 16], 128),
                                   ([128, 128], 64), ([64, 64, 128], 128), ([128], 128),
                                   ([128, 128, 128], 128), ([128, 128, 128, 128], 128),
-                                  ([64, 256, 64], 128)])
+                                  ([64, 256, 64], 128), ([32], 64), ([32, 64], 64)])
 @pytest.mark.parametrize("n", [1, 37, 1000, 20000])
 def test_linear_fwd_bwd_matches_torch(ks, h, n):
     gen = torch.Generator().manual_seed(n + h)
@@ -1270,7 +1270,7 @@ def test_gather_multi_equals_single_calls(d):
         assert torch.equal(o, r)
 
 
-@pytest.mark.parametrize("case", ["pair", "pair_root", "small", "k_differs", "w_differs"])
+@pytest.mark.parametrize("case", ["pair", "pair_root", "small", "k_differs", "w_differs", "k256"])
 def test_linear_multi_equals_per_job_calls(case):
     """hgnn_linear_fwd_multi / hgnn_linear_bwd_multi (a sampled layer's two destination types'
     K3 as one launch per column block, round 6) against one hgnn_linear_fwd_mask /
@@ -1278,14 +1278,16 @@ def test_linear_multi_equals_per_job_calls(case):
     the grid: bitwise.  dW / db are the same partial sums over a different block split (the pair
     shares one chip's worth of blocks): within 2e-6 of the largest entry.  'k_differs' (K = 384
     beside K = 512) and 'w_differs' (one job without weight gradients: a different kernel
-    variant) run job by job: bitwise throughout."""
+    variant) run job by job: bitwise throughout.  So does 'k256' (cfg4's two destination types at
+    K = 256, which are not paired)."""
     gen = torch.Generator().manual_seed(7)
     h = 128
     shapes = {"pair": [(9000, [128, 128, 128]), (12345, [128, 128, 128])],
               "pair_root": [(8192, [128, 128, 128]), (20000, [128, 128, 128])],
               "k_differs": [(9000, [128, 128, 128]), (10000, [128, 128, 128, 128])],
               "small": [(3000, [128, 128, 128]), (2500, [128, 128, 128])],
-              "w_differs": [(9000, [128, 128, 128]), (7000, [128, 128, 128])]}[case]
+              "w_differs": [(9000, [128, 128, 128]), (7000, [128, 128, 128])],
+              "k256": [(9000, [128, 128]), (12345, [128, 128])]}[case]
     jobs_f, ref_f = [], []
     for n, ks in shapes:
         segs = [torch.randn(n, k, generator=gen).to(DEV) for k in ks]
@@ -1316,7 +1318,7 @@ def test_linear_multi_equals_per_job_calls(case):
         for d, r in zip(job[4], dxs_ref):
             if d is not None:
                 assert torch.equal(d, r)
-        exact = case in ("k_differs", "w_differs")
+        exact = case in ("k_differs", "w_differs", "k256")
         for a, r in ((dw, rdw), (db, rdb)):
             if r is None:
                 assert a is None

@@ -1,5 +1,6 @@
-// K3 (fused multi-segment linear) types and bf16-split helpers shared by linear.hip (the f32-input
-// MFMA kernels, the general shapes and the C ABI) and linear_xs.hip (the split-once kernels).
+// K3 (fused multi-segment linear) types, bf16-split helpers and the kernel families' launchers,
+// shared by linear.hip (argument checks, path choice, the C ABI), linear_general.hip / linear_v4.hip
+// (the f32-input MFMA kernels: any shape / compile-time shapes) and linear_xs.hip (split-once).
 #pragma once
 #include "hgnn_common.h"
 
@@ -10,6 +11,10 @@ namespace hgnn {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short bf16x8_t __attribute__((ext_vector_type(8)));
 typedef short bf16x4_t __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
 
 struct Seg {
   const float* x;
@@ -219,5 +224,28 @@ int xs_linear_bwd2(const LinArgs (&a)[2], const ChunkTab (&tab)[2], bool dx, int
                    hipStream_t stream);
 // the split kernels' backward variant of a job: bit 0 dgrad, bit 1 wgrad, bit 2 accumulate
 int xs_bwd_class(const LinArgs& a, const ChunkTab& tab, bool dx);
+
+// The f32-input families' launchers; the caller validated the arguments and chose the family.
+// A backward launcher writes dX (dx) and, with wg, *slabs blocks of dW / db partials, [H][K + 1]
+// each, into the workspace, which it checks against that count; the caller reduces them.
+inline size_t slab_bytes(int64_t slabs, int32_t h, int32_t k_total) {
+  return (size_t)slabs * h * (k_total + 1) * 4;
+}
+// General (linear_general.hip): any shape; vec = every row float4-aligned.
+int gen_linear_fwd(const LinArgs& a, bool vec, hipStream_t stream);
+int gen_linear_bwd(LinArgs a, bool vec, bool dx, bool wg, void* ws, size_t ws_bytes,
+                   int64_t* slabs, hipStream_t stream);
+int64_t gen_bwd_slabs(int64_t n_rows, int32_t k_total, int32_t h);
+// the backward's LDS fast path (linear_general.hip): weight gradients wanted, and lds_bwd_ok
+int lds_linear_bwd(LinArgs a, bool dx, void* ws, size_t ws_bytes, int64_t* slabs,
+                   hipStream_t stream);
+bool lds_bwd_ok(const LinArgs& a, bool vec);
+int64_t lds_bwd_slabs(int64_t n_rows);
+// v4 / v5 (linear_v4.hip): H in {64, 128}, K in {64, 128, 256}, 16-column chunks (tab).  The
+// slab count depends on the kernel v4_linear_bwd picks: v4_bwd_max_slabs is the largest.
+int v4_linear_fwd(const LinArgs& a, const ChunkTab& tab, hipStream_t stream);
+int v4_linear_bwd(LinArgs a, const ChunkTab& tab, bool dx, bool wg, void* ws, size_t ws_bytes,
+                  int64_t* slabs, hipStream_t stream);
+int64_t v4_bwd_max_slabs();
 
 }  // namespace hgnn

@@ -589,31 +589,74 @@ def _check_rows(segs, n, what):
             raise ValueError(f"{what}: segment {i} is {tuple(s_.shape)}, expected {n} rows")
 
 
+def _lin_fwd_job(what, segs, w, b, add=None, mask_out=None):
+    """One K3 forward's shape checks (errors named after the caller, ``what``), its output buffer
+    and its traffic / flop counts for the kernel timer: ``(n, h, ks, out, nbytes, flops)``."""
+    n = int(segs[0].shape[0])
+    h = int(w.shape[0])
+    ks = [int(s.shape[1]) for s in segs]
+    k = sum(ks)
+    if w.shape[1] != k:
+        raise ValueError(f"weight has {w.shape[1]} input columns, segments sum to {k}")
+    _check_rows(segs, n, what)
+    if add is not None and tuple(add.shape) != (n, h):
+        raise ValueError(f"{what}: add is {tuple(add.shape)}, expected {(n, h)}")
+    if b is not None and b.numel() != h:
+        raise ValueError(f"{what}: bias has {b.numel()} entries, expected {h}")
+    out = torch.empty(n, h, dtype=torch.float32, device=w.device)
+    nb = 4 * n * (k + h + (h if add is not None else 0)) + (16 * n if mask_out is not None else 0)
+    return n, h, ks, out, nb, 2 * n * k * h
+
+
 def linear_fwd(segs: Sequence[torch.Tensor], w: torch.Tensor, b: Optional[torch.Tensor],
                relu: bool, add: Optional[torch.Tensor] = None,
                mask_out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """K3/K4: ``act(sum_s segs[s] @ w[:, seg s]^T + b (+ add))``; ``mask_out`` (from
     :func:`relu_mask_for`) also receives the ReLU mask as bits."""
-    n = int(segs[0].shape[0])
-    h = int(w.shape[0])
-    ks = [int(s.shape[1]) for s in segs]
-    if w.shape[1] != sum(ks):
-        raise ValueError(f"weight has {w.shape[1]} input columns, segments sum to {sum(ks)}")
-    _check_rows(segs, n, "linear_fwd")
-    if add is not None and tuple(add.shape) != (n, h):
-        raise ValueError(f"linear_fwd: add is {tuple(add.shape)}, expected {(n, h)}")
-    if b is not None and b.numel() != h:
-        raise ValueError(f"linear_fwd: bias has {b.numel()} entries, expected {h}")
-    dev = w.device
-    out = torch.empty(n, h, dtype=torch.float32, device=dev)
-    k = sum(ks)
-    nb = 4 * n * (k + h + (h if add is not None else 0)) + (16 * n if mask_out is not None else 0)
-    with _timed(f"linear_fwd[{n}x{k}->{h}]", nb, flops=2 * n * k * h):
+    n, h, ks, out, nb, fl = _lin_fwd_job("linear_fwd", segs, w, b, add, mask_out)
+    with _timed(f"linear_fwd[{n}x{sum(ks)}->{h}]", nb, flops=fl):
         N.check(N.lib().hgnn_linear_fwd_mask(len(segs), N.ptr_array(segs), N.int_array(ks), n,
                                              N.ptr(w), h, N.ptr(b), N.ptr(add),
                                              1 if relu else 0, N.ptr(out), N.ptr(mask_out),
-                                             N.stream_ptr(dev)), "hgnn_linear_fwd_mask")
+                                             N.stream_ptr(w.device)), "hgnn_linear_fwd_mask")
     return out
+
+
+def _lin_bwd_job(what, segs, w, dout, out_act, dxs, need_w, need_b, dz_out=None, mask=None,
+                 dx_add=()):
+    """One K3 backward's shape checks (errors named after the caller, ``what``), its weight
+    gradient buffers, its accumulate bits and its traffic / flop counts for the kernel timer:
+    ``(n, h, ks, dw, db, acc, nbytes, flops)``."""
+    n = int(segs[0].shape[0])
+    h = int(w.shape[0])
+    ks = [int(s.shape[1]) for s in segs]
+    k = sum(ks)
+    if w.shape[1] != k:
+        raise ValueError(f"weight has {w.shape[1]} input columns, segments sum to {k}")
+    _check_rows(segs, n, what)
+    for name, t in (("dout", dout), ("out_act", out_act), ("dz_out", dz_out)):
+        if t is not None and tuple(t.shape) != (n, h):
+            raise ValueError(f"{what}: {name} is {tuple(t.shape)}, expected {(n, h)}")
+    if len(dxs) != len(segs):
+        raise ValueError(f"{what}: {len(dxs)} dx buffers for {len(segs)} segments")
+    for s_, dx in zip(segs, dxs):
+        if dx is not None and tuple(dx.shape) != tuple(s_.shape):
+            raise ValueError(f"{what}: dx {tuple(dx.shape)} for a {tuple(s_.shape)} segment")
+    if mask is not None and tuple(mask.shape) != (n, 4):
+        raise ValueError(f"{what}: ReLU bits are {tuple(mask.shape)}, expected {(n, 4)}")
+    dw = torch.empty_like(w) if need_w else None
+    db = torch.empty(h, dtype=torch.float32, device=w.device) if need_b else None
+    k_dx = sum(kk for kk, dx in zip(ks, dxs) if dx is not None)
+    bits = mask is not None and out_act is not None
+    nb = 4 * n * (h + (h if out_act is not None and not bits else 0) + k + k_dx) + \
+        (16 * n if bits else 0) + (4 * n * h if dz_out is not None else 0)
+    fl = 2 * n * h * k_dx + (2 * n * k * h if need_w else 0)   # dgrad + wgrad
+    acc = 0
+    for i, on in enumerate(dx_add):
+        if on and dxs[i] is not None:
+            acc |= 1 << i
+            nb += 4 * n * ks[i]          # the gradient already there is read back
+    return n, h, ks, dw, db, acc, nb, fl
 
 
 def linear_bwd(segs, w, dout, out_act, dxs: Sequence[Optional[torch.Tensor]], need_w: bool,
@@ -622,38 +665,12 @@ def linear_bwd(segs, w, dout, out_act, dxs: Sequence[Optional[torch.Tensor]], ne
     """K3 backward; ``dz_out`` (optional [n, h]) receives the masked dz as well; ``mask``: the
     forward's ReLU bits (read instead of ``out_act`` by the persistent kernels); ``dx_add[s]``:
     segment s's input gradient is added into what ``dxs[s]`` holds (``hgnn_linear_bwd_ex``)."""
-    n = int(segs[0].shape[0])
-    h = int(w.shape[0])
-    ks = [int(s.shape[1]) for s in segs]
-    if w.shape[1] != sum(ks):
-        raise ValueError(f"weight has {w.shape[1]} input columns, segments sum to {sum(ks)}")
-    _check_rows(segs, n, "linear_bwd")
-    for what, t in (("dout", dout), ("out_act", out_act), ("dz_out", dz_out)):
-        if t is not None and tuple(t.shape) != (n, h):
-            raise ValueError(f"linear_bwd: {what} is {tuple(t.shape)}, expected {(n, h)}")
-    if len(dxs) != len(segs):
-        raise ValueError(f"linear_bwd: {len(dxs)} dx buffers for {len(segs)} segments")
-    for s_, dx in zip(segs, dxs):
-        if dx is not None and tuple(dx.shape) != tuple(s_.shape):
-            raise ValueError(f"linear_bwd: dx {tuple(dx.shape)} for a {tuple(s_.shape)} segment")
-    if mask is not None and tuple(mask.shape) != (n, 4):
-        raise ValueError(f"linear_bwd: ReLU bits are {tuple(mask.shape)}, expected {(n, 4)}")
+    n, h, ks, dw, db, acc, nb, fl = _lin_bwd_job("linear_bwd", segs, w, dout, out_act, dxs,
+                                                 need_w, need_b, dz_out, mask, dx_add)
     dev = w.device
-    dw = torch.empty_like(w) if need_w else None
-    db = torch.empty(h, dtype=torch.float32, device=dev) if need_b else None
     ws = None
     if need_w or need_b:
         ws = N.workspace(N.lib().hgnn_linear_bwd_ws_bytes(n, sum(ks), h), dev)
-    k_dx = sum(k for k, dx in zip(ks, dxs) if dx is not None)
-    bits = mask is not None and out_act is not None
-    nb = 4 * n * (h + (h if out_act is not None and not bits else 0) + sum(ks) + k_dx) + \
-        (16 * n if bits else 0) + (4 * n * h if dz_out is not None else 0)
-    fl = 2 * n * h * k_dx + (2 * n * sum(ks) * h if need_w else 0)   # dgrad + wgrad
-    acc = 0
-    for i, on in enumerate(dx_add):
-        if on and dxs[i] is not None:
-            acc |= 1 << i
-            nb += 4 * n * ks[i]          # the gradient already there is read back
     with _timed(f"linear_bwd[{n}x{sum(ks)}->{h}]", nb, flops=fl):
         N.check(N.lib().hgnn_linear_bwd_ex(
             len(segs), N.ptr_array(segs), N.int_array(ks), n, N.ptr(w), h, N.ptr(dout),
@@ -669,30 +686,18 @@ def linear_fwd_many(jobs) -> List[torch.Tensor]:
     512 split path share each column block's launch; anything else runs job by job there."""
     if len(jobs) == 1 or len({int(j[1].shape[0]) for j in jobs}) > 1:   # (one output width)
         return [linear_fwd(segs, w, b, relu, mask_out=mk) for segs, w, b, relu, mk in jobs]
-    outs, n_seg, xs, ks, rows, ws_, bs, relus, mks = [], [], [], [], [], [], [], [], []
-    nb = fl = 0
-    for segs, w, b, relu, mk in jobs:
-        n, h = int(segs[0].shape[0]), int(w.shape[0])
-        k = [int(s_.shape[1]) for s_ in segs]
-        if w.shape[1] != sum(k):
-            raise ValueError(f"weight has {w.shape[1]} input columns, segments sum to {sum(k)}")
-        _check_rows(segs, n, "linear_fwd_many")
-        if b is not None and b.numel() != h:
-            raise ValueError(f"linear_fwd_many: bias has {b.numel()} entries, expected {h}")
-        out = torch.empty(n, h, dtype=torch.float32, device=w.device)
-        outs.append(out)
-        n_seg.append(len(segs)); xs.extend(segs); ks.extend(k); rows.append(n)
-        ws_.append(w); bs.append(b); relus.append(1 if relu else 0); mks.append(mk)
-        nb += 4 * n * (sum(k) + h) + (16 * n if mk is not None else 0)
-        fl += 2 * n * sum(k) * h
-    dev = jobs[0][1].device
-    h = int(jobs[0][1].shape[0])
+    info = [_lin_fwd_job("linear_fwd_many", segs, w, b, mask_out=mk) for segs, w, b, _, mk in jobs]
+    rows, outs = [i[0] for i in info], [i[3] for i in info]
+    ks = [k for i in info for k in i[2]]
+    dev, h = jobs[0][1].device, info[0][1]
     with _timed(f"linear_fwd_multi[{'+'.join(str(r) for r in rows)}x{sum(ks) // len(jobs)}->{h}]",
-                nb, flops=fl):
+                sum(i[4] for i in info), flops=sum(i[5] for i in info)):
         N.check(N.lib().hgnn_linear_fwd_multi(
-            len(jobs), N.int_array(n_seg), N.ptr_array(xs), N.int_array(ks), N.i64_array(rows),
-            N.ptr_array(ws_), h, N.ptr_array(bs), N.int_array(relus), N.ptr_array(outs),
-            N.ptr_array(mks), N.stream_ptr(dev)), "hgnn_linear_fwd_multi")
+            len(jobs), N.int_array([len(j[0]) for j in jobs]),
+            N.ptr_array([s_ for j in jobs for s_ in j[0]]), N.int_array(ks), N.i64_array(rows),
+            N.ptr_array([j[1] for j in jobs]), h, N.ptr_array([j[2] for j in jobs]),
+            N.int_array([1 if j[3] else 0 for j in jobs]), N.ptr_array(outs),
+            N.ptr_array([j[4] for j in jobs]), N.stream_ptr(dev)), "hgnn_linear_fwd_multi")
     return outs
 
 
@@ -703,48 +708,27 @@ def linear_bwd_many(jobs):
     if len(jobs) == 1 or len({int(j[1].shape[0]) for j in jobs}) > 1:
         return [linear_bwd(segs, w, dout, out_act, dxs, need_w, need_b, mask=mk)
                 for segs, w, dout, out_act, dxs, need_w, need_b, mk in jobs]
-    n_seg, xs, ks, rows, kt, ws_, douts, outs, mks, dxs_all, dws, dbs = ([] for _ in range(12))
-    nb = fl = 0
-    h = int(jobs[0][1].shape[0])
-    for segs, w, dout, out_act, dxs, need_w, need_b, mk in jobs:
-        n = int(segs[0].shape[0])
-        k = [int(s_.shape[1]) for s_ in segs]
-        if w.shape[1] != sum(k):
-            raise ValueError(f"weight has {w.shape[1]} input columns, segments sum to {sum(k)}")
-        _check_rows(segs, n, "linear_bwd_many")
-        for what, t in (("dout", dout), ("out_act", out_act)):
-            if t is not None and tuple(t.shape) != (n, h):
-                raise ValueError(f"linear_bwd_many: {what} is {tuple(t.shape)}, expected {(n, h)}")
-        if len(dxs) != len(segs):
-            raise ValueError(f"linear_bwd_many: {len(dxs)} dx buffers for {len(segs)} segments")
-        for s_, dx in zip(segs, dxs):
-            if dx is not None and tuple(dx.shape) != tuple(s_.shape):
-                raise ValueError(f"linear_bwd_many: dx {tuple(dx.shape)} for a "
-                                 f"{tuple(s_.shape)} segment")
-        if mk is not None and tuple(mk.shape) != (n, 4):
-            raise ValueError(f"linear_bwd_many: ReLU bits are {tuple(mk.shape)}, expected {(n, 4)}")
-        n_seg.append(len(segs)); xs.extend(segs); ks.extend(k); rows.append(n); kt.append(sum(k))
-        ws_.append(w); douts.append(dout); outs.append(out_act)
-        mks.append(mk if out_act is not None else None); dxs_all.extend(dxs)
-        dws.append(torch.empty_like(w) if need_w else None)
-        dbs.append(torch.empty(h, dtype=torch.float32, device=w.device) if need_b else None)
-        k_dx = sum(kk for kk, dx in zip(k, dxs) if dx is not None)
-        bits = mk is not None and out_act is not None
-        nb += 4 * n * (h + (h if out_act is not None and not bits else 0) + sum(k) + k_dx) + \
-            (16 * n if bits else 0)
-        fl += 2 * n * h * k_dx + (2 * n * sum(k) * h if need_w else 0)
-    dev = jobs[0][1].device
+    info = [_lin_bwd_job("linear_bwd_many", segs, w, dout, out_act, dxs, need_w, need_b, mask=mk)
+            for segs, w, dout, out_act, dxs, need_w, need_b, mk in jobs]
+    rows, kt = [i[0] for i in info], [sum(i[2]) for i in info]
+    dws, dbs = [i[3] for i in info], [i[4] for i in info]
+    dev, h = jobs[0][1].device, info[0][1]
     ws = None
     if any(d is not None for d in dws + dbs):
         ws = N.workspace(N.lib().hgnn_linear_bwd_multi_ws_bytes(
             len(jobs), N.i64_array(rows), N.int_array(kt), h), dev)
     with _timed(f"linear_bwd_multi[{'+'.join(str(r) for r in rows)}x{sum(kt) // len(jobs)}->{h}]",
-                nb, flops=fl):
+                sum(i[6] for i in info), flops=sum(i[7] for i in info)):
         N.check(N.lib().hgnn_linear_bwd_multi(
-            len(jobs), N.int_array(n_seg), N.ptr_array(xs), N.int_array(ks), N.i64_array(rows),
-            N.ptr_array(ws_), h, N.ptr_array(douts), N.ptr_array(outs), N.ptr_array(mks),
-            N.ptr_array(dxs_all), None, N.ptr_array(dws), N.ptr_array(dbs), N.ptr(ws),
-            0 if ws is None else ws.numel(), N.stream_ptr(dev)), "hgnn_linear_bwd_multi")
+            len(jobs), N.int_array([len(j[0]) for j in jobs]),
+            N.ptr_array([s_ for j in jobs for s_ in j[0]]),
+            N.int_array([k for i in info for k in i[2]]), N.i64_array(rows),
+            N.ptr_array([j[1] for j in jobs]), h, N.ptr_array([j[2] for j in jobs]),
+            N.ptr_array([j[3] for j in jobs]),
+            N.ptr_array([j[7] if j[3] is not None else None for j in jobs]),
+            N.ptr_array([d for j in jobs for d in j[4]]), None, N.ptr_array(dws),
+            N.ptr_array(dbs), N.ptr(ws), 0 if ws is None else ws.numel(), N.stream_ptr(dev)),
+            "hgnn_linear_bwd_multi")
     return list(zip(dws, dbs))
 
 
