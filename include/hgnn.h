@@ -690,10 +690,24 @@ size_t hgnn_score_topk_lds_bytes(int32_t d, int32_t L);
 int hgnn_score_topk(const float* U, const int32_t* rows, int64_t n_rows, const float* P,
                     int64_t n_cand, int32_t d, int32_t L, float* topv, int32_t* topi,
                     hgnn_stream_t stream);
-/* Recall / NDCG (as hgnn_topk_metrics) from hgnn_score_topk lists with L = min(K, n_cand) + 1
- * (or min(K, n_cand) when n_cand <= K).  A row whose K-th value ties the (K+1)-th needs the whole
- * row for sklearn's tie groups: it gets tie_flag = 1 and no outputs; redo those rows with
- * materialised scores (hgnn_topk_metrics_rows). */
+/* hgnn_score_topk over bf16 tables (uint16_t bit patterns, as the bf16 row storage above): the
+ * scores come from bf16 MFMA (16x16x32) with fp32 accumulation, so a list is what hgnn_score_topk
+ * gives on the widened tables float(U), float(P), up to fp32 summation order.  topv / topi stay
+ * fp32 / int32, so hgnn_topk_finish takes them as they are.  Same contract otherwise: d in
+ * {64, 128}; U and P row-major, 16-B aligned; 1 <= L <= min(64, n_cand); score desc then index
+ * asc; no sync, no allocation, graph-capturable; the same argument checks and error codes.  A
+ * workgroup takes 128 users (8 waves x 16) and streams the candidates in chunks of 64 or, where
+ * that lets one more workgroup live on the CU, 32; hgnn_score_topk_bf16_lds_bytes is the dynamic
+ * LDS of the (d, L) launch: two chunk buffers and 128 L 8 B of lists, <= 160 KiB for every legal
+ * L. */
+size_t hgnn_score_topk_bf16_lds_bytes(int32_t d, int32_t L);
+int hgnn_score_topk_bf16(const uint16_t* U, const int32_t* rows, int64_t n_rows,
+                         const uint16_t* P, int64_t n_cand, int32_t d, int32_t L, float* topv,
+                         int32_t* topi, hgnn_stream_t stream);
+/* Recall / NDCG (as hgnn_topk_metrics) from hgnn_score_topk or hgnn_score_topk_bf16 lists with
+ * L = min(K, n_cand) + 1 (or min(K, n_cand) when n_cand <= K).  A row whose K-th value ties the
+ * (K+1)-th needs the whole row for sklearn's tie groups: it gets tie_flag = 1 and no outputs;
+ * redo those rows with materialised scores (hgnn_topk_metrics_rows). */
 int hgnn_topk_finish(const float* topv, const int32_t* topi, int64_t n_rows, int32_t L,
                      int64_t n_cand, int32_t K, const int32_t* true_rowptr,
                      const int32_t* true_cand, const int32_t* true_count, double* recall,

@@ -439,6 +439,196 @@ __global__ void __launch_bounds__(kStThreads) k_score_topk(const ScoreTopkArgs a
   }
 }
 
+// ---- the same on bf16 rows: scores on v_mfma_f32_16x16x32_bf16 ------------------------------
+// U and P are bf16 tables (uint16_t bit patterns); products are exact and the accumulation is
+// fp32, so a score is the fp32 dot product of the widened rows up to summation order.  Candidates
+// are again the A operand and users the B operand: lane (i, g) holds 8 consecutive k of row i
+// (k = 32c + 8g + j, one 16-B read per k-step), and the C/D mapping (col = lane & 15,
+// row = 4 (lane >> 4) + reg) gives each lane 4 candidates x 1 user per tile, so the rejection
+// test and the list inserts are those of k_score_topk.
+// A tile costs D/32 MFMAs of 16 cycles instead of D/4 of 32, and what is left is the inserts: a
+// chain of LDS reads, a ballot, shuffles and LDS writes per entry, one entry at a time per wave.
+// Only more waves hide that latency, so a wave takes ONE 16-user tile (half the fp32 kernel's 32)
+// and a workgroup is 8 waves = 128 users; wider waves (32 / 64 users) and wider workgroups (256 /
+// 512 users), which would cut the candidate stream, all measured slower.  For the
+// same reason the chunk shrinks from 64 to 32 candidates where the smaller buffers let one more
+// workgroup live on the CU (st16_chunk).
+// LDS rows are D + 16 halfwords: consecutive rows sit 32 B apart mod 256, which is conflict-free
+// for the ds_read_b128 fragment reads under their lane groups ({0-3, 12-15, 20-27}, ...); a pad
+// of 8 halfwords (16 B) would leave them 2-way (the K3 planes).
+typedef short st_bf16x8 __attribute__((ext_vector_type(8)));
+
+struct ScoreTopkBf16Args {
+  const uint16_t* U;      // [n_u_rows][d] user embeddings, bf16
+  const int32_t* rows;    // null, or the U row of each output row
+  int64_t n_rows;
+  const uint16_t* P;      // [>= n_cand][d] candidate embeddings, bf16
+  int64_t n_cand;
+  int32_t L;              // list length, 1..64
+  float* topv;            // [n_rows][L] scores, best first
+  int32_t* topi;          // [n_rows][L] candidate indices
+};
+
+constexpr int kSt16Waves = 8;
+constexpr int kSt16Threads = kSt16Waves * 64;
+constexpr int kSt16Users = kSt16Waves * 16;        // per workgroup
+constexpr size_t kSt16LdsLimit = 160 * 1024;      // one CU's LDS
+
+#ifndef HGNN_ST16_TC
+#define HGNN_ST16_TC 0    // A/B builds: 32 / 64 forces the chunk
+#endif
+
+// two chunk buffers of tc padded rows + the lists
+constexpr size_t st16_lds_bytes(int d, int L, int tc) {
+  return (size_t)2 * tc * (d + 16) * 2 + (size_t)kSt16Users * L * 8;
+}
+
+// Workgroups of this (d, L, chunk) that fit a CU: by LDS, and by wave slots (4 x 8 waves fill the
+// CU's 32; the d = 128, 64-candidate kernel holds 68 VGPRs, 7 waves per SIMD: 3 workgroups).
+inline int st16_resident(int d, int L, int tc) {
+  const int by_lds = (int)(kSt16LdsLimit / st16_lds_bytes(d, L, tc));
+  const int cap = (d == 128 && tc == 64) ? 3 : 4;
+  return by_lds < cap ? by_lds : cap;
+}
+
+// Candidates per chunk: 64 (half the barriers), or 32 where that makes room for a workgroup more.
+inline int st16_chunk(int d, int L) {
+  if (HGNN_ST16_TC == 32 || HGNN_ST16_TC == 64) return HGNN_ST16_TC;
+  return st16_resident(d, L, 32) > st16_resident(d, L, 64) ? 32 : 64;
+}
+
+template <int D, int TC>
+__global__ void __launch_bounds__(kSt16Threads) k_score_topk_bf16(const ScoreTopkBf16Args a) {
+  constexpr int S = D + 16;                     // LDS row stride, halfwords
+  constexpr int KS = D / 32;                    // k-steps (MFMAs) per tile
+  constexpr int MT = 2;                         // tiles whose MFMA chains interleave (4: slower)
+  constexpr int PIECES = TC * D / 8;            // 16-B pieces per chunk
+  constexpr int LOADS = (PIECES + kSt16Threads - 1) / kSt16Threads;
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  uint16_t* cbuf = reinterpret_cast<uint16_t*>(lds);                    // [2][TC][S]
+  float* lv_all = reinterpret_cast<float*>(cbuf + 2 * TC * S);          // [8 waves][16 users][L]
+  const int L = a.L;
+  int* li_all = reinterpret_cast<int*>(lv_all + kSt16Users * L);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = lane & 15, g = lane >> 4;
+  const int64_t row0 = (int64_t)blockIdx.x * kSt16Users + wave * 16;
+  float* lvw = lv_all + wave * 16 * L;
+  int* liw = li_all + wave * 16 * L;
+  for (int e = lane; e < 16 * L; e += 64) { lvw[e] = -FLT_MAX; liw[e] = INT_MAX; }
+  // user fragments (B operand): lane (i, g) holds user i's columns 32c + 8g .. +7
+  st_bf16x8 uf[KS];
+  float thr;
+  {
+    const int64_t r = row0 + i;
+    const bool ok = r < a.n_rows;
+    const int64_t ur = ok ? (a.rows ? (int64_t)a.rows[r] : r) : 0;
+#pragma unroll
+    for (int c = 0; c < KS; ++c)
+      uf[c] = ok ? *reinterpret_cast<const st_bf16x8*>(a.U + ur * D + c * 32 + 8 * g)
+                 : st_bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    thr = ok ? -FLT_MAX : FLT_MAX;   // rows past the end never take anything
+  }
+  const int64_t C = a.n_cand;
+  const int64_t n_chunks = (C + TC - 1) / TC;
+  // chunk staging: thread t loads 16-B piece t + 512 q of the chunk (row-major TC x D)
+  uint4 nxt[LOADS];
+  auto load_chunk = [&](int64_t ch) {
+#pragma unroll
+    for (int q = 0; q < LOADS; ++q) {
+      const int f = threadIdx.x + kSt16Threads * q;
+      const int rr = f / (D / 8), cc = (f % (D / 8)) * 8;
+      const int64_t cand = ch * TC + rr;
+      nxt[q] = (f < PIECES && cand < C) ? *reinterpret_cast<const uint4*>(a.P + cand * D + cc)
+                                        : make_uint4(0u, 0u, 0u, 0u);
+    }
+  };
+  auto store_chunk = [&](int buf) {
+#pragma unroll
+    for (int q = 0; q < LOADS; ++q) {
+      const int f = threadIdx.x + kSt16Threads * q;
+      const int rr = f / (D / 8), cc = (f % (D / 8)) * 8;
+      if (f < PIECES) *reinterpret_cast<uint4*>(cbuf + buf * TC * S + rr * S + cc) = nxt[q];
+    }
+  };
+  load_chunk(0);
+  store_chunk(0);
+  __syncthreads();
+  for (int64_t ch = 0; ch < n_chunks; ++ch) {
+    const int buf = (int)(ch & 1);
+    if (ch + 1 < n_chunks) load_chunk(ch + 1);   // in flight during the work below
+    const uint16_t* cb = cbuf + buf * TC * S;
+    const bool ragged = (ch + 1) * TC > C;       // only the last chunk can hold rows past C
+#pragma unroll
+    for (int t = 0; t < TC / 16; t += MT) {
+      f32x4 acc[MT];
+#pragma unroll
+      for (int tt = 0; tt < MT; ++tt) acc[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < KS; ++c) {
+        st_bf16x8 pv[MT];
+#pragma unroll
+        for (int tt = 0; tt < MT; ++tt)
+          pv[tt] = *reinterpret_cast<const st_bf16x8*>(cb + ((t + tt) * 16 + i) * S + c * 32 +
+                                                       8 * g);
+#pragma unroll
+        for (int tt = 0; tt < MT; ++tt)
+          acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pv[tt], uf[c], acc[tt], 0, 0, 0);
+      }
+      // lane (i, g): acc[tt][j] = score(candidate ch*TC + (t+tt)*16 + 4g + j, user i)
+#pragma unroll
+      for (int tt = 0; tt < MT; ++tt) {
+        if (ragged) {   // wave-uniform
+          const int64_t cbase = ch * TC + (t + tt) * 16 + 4 * g;
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (cbase + j >= C) acc[tt][j] = -__builtin_inff();   // never >= any thr
+        }
+        const f32x4 v = acc[tt];
+        const bool any = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])) >= thr;
+        if (__ballot(any) == 0ull) continue;   // wave-uniform: the common case
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float val = v[j];
+          unsigned long long cm = __ballot(val >= thr);
+          while (cm) {
+            const int src = __ffsll((long long)cm) - 1;
+            const int u = src & 15;
+            const float cs = __shfl(val, src, 64);
+            const int ci = (int)(ch * TC + (t + tt) * 16 + 4 * (src >> 4) + j);
+            float nthr;
+            st_insert(lvw + u * L, liw + u * L, L, lane, cs, ci, nthr);
+            if (i == u) thr = fmaxf(thr, nthr);
+            cm = __ballot(val >= thr) & (~0ull << src << 1);
+          }
+        }
+      }
+    }
+    if (ch + 1 < n_chunks) {
+      // the other buffer held chunk ch - 1, which every wave finished before the barrier that
+      // ended the previous iteration: one barrier per chunk
+      store_chunk(buf ^ 1);
+      __syncthreads();
+    }
+  }
+  // write the lists
+  for (int u = 0; u < 16; ++u) {
+    const int64_t r = row0 + u;
+    if (r >= a.n_rows) break;
+    if (lane < L) {
+      a.topv[r * L + lane] = lvw[u * L + lane];
+      a.topi[r * L + lane] = liw[u * L + lane];
+    }
+  }
+}
+
+template <int D>
+static void launch_score_topk_bf16(int tc, unsigned blocks, size_t lds, hipStream_t stream,
+                                   const ScoreTopkBf16Args& a) {
+  const dim3 grid(blocks), block(kSt16Threads);
+  if (tc == 32) hipLaunchKernelGGL((k_score_topk_bf16<D, 32>), grid, block, lds, stream, a);
+  else hipLaunchKernelGGL((k_score_topk_bf16<D, 64>), grid, block, lds, stream, a);
+}
+
 // Metrics from the fused lists: one wave per row; rows where a tie crosses the cut get
 // tie_flag = 1 and nothing else (the caller redoes them from materialised scores).
 __global__ void __launch_bounds__(256) k_topk_finish(const TopkArgs a, const float* topv,
@@ -520,6 +710,32 @@ int hgnn_score_topk(const float* U, const int32_t* rows, int64_t n_rows, const f
   if (d == 64) hipLaunchKernelGGL(k_score_topk<64>, grid, block, lds, stream, a);
   else hipLaunchKernelGGL(k_score_topk<128>, grid, block, lds, stream, a);
   return check_launch("k_score_topk");
+}
+
+size_t hgnn_score_topk_bf16_lds_bytes(int32_t d, int32_t L) {
+  return st16_lds_bytes(d, L, st16_chunk(d, L));
+}
+
+int hgnn_score_topk_bf16(const uint16_t* U, const int32_t* rows, int64_t n_rows,
+                         const uint16_t* P, int64_t n_cand, int32_t d, int32_t L, float* topv,
+                         int32_t* topi, hgnn_stream_t stream_) {
+  hipStream_t stream = as_stream(stream_);
+  if (n_rows < 0 || n_cand < 1 || n_cand >= INT_MAX || L < 1 || L > 64 || L > n_cand)
+    return fail(HGNN_E_ARG, "score_topk_bf16: rows=%lld cand=%lld L=%d", (long long)n_rows,
+                (long long)n_cand, L);
+  if (d != 64 && d != 128)
+    return fail(HGNN_E_UNSUPPORTED, "score_topk_bf16: d=%d (64 or 128)", d);
+  if (n_rows == 0) return HGNN_OK;
+  if (!U || !P || !topv || !topi) return fail(HGNN_E_ARG, "score_topk_bf16: null pointer");
+  if (reinterpret_cast<uintptr_t>(U) % 16 || reinterpret_cast<uintptr_t>(P) % 16)
+    return fail(HGNN_E_ARG, "score_topk_bf16: U and P must be 16-B aligned");
+  ScoreTopkBf16Args a{U, rows, n_rows, P, n_cand, L, topv, topi};
+  const int tc = st16_chunk(d, L);
+  const size_t lds = st16_lds_bytes(d, L, tc);
+  const unsigned blocks = (unsigned)cdiv(n_rows, kSt16Users);
+  if (d == 64) launch_score_topk_bf16<64>(tc, blocks, lds, stream, a);
+  else launch_score_topk_bf16<128>(tc, blocks, lds, stream, a);
+  return check_launch("k_score_topk_bf16");
 }
 
 int hgnn_topk_finish(const float* topv, const int32_t* topi, int64_t n_rows, int32_t L,

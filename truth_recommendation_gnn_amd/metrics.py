@@ -8,6 +8,10 @@ candidate on MFMA and keeps each user's top-(K+1) list without materialising the
 The rare rows whose K-th score ties the next (sklearn's tie groups then need the whole row) and
 other widths take the materialised path: one GEMM per user batch (torch.mm -> hipBLASLt) and
 ``hgnn_topk_metrics`` over it.  Same arguments, same return values.
+
+``row_dtype="bf16"`` (or ``torch.bfloat16`` tables) ranks the rows rounded to bf16: the fused
+kernel is then ``hgnn_score_topk_bf16`` (bf16 MFMA, fp32 accumulation, fp32 lists), everything
+else runs as above on the fp32 widening of the rounded rows.  The default stays fp32.
 """
 from __future__ import annotations
 
@@ -17,6 +21,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _native as N
+from . import ops
 
 
 class _Grouped:
@@ -44,6 +49,33 @@ class _Grouped:
         self.true_cand = (key % max(C, 1)).to(torch.int32)
 
 
+class _Default(str):
+    """The ``row_dtype`` default: the string "fp32", told apart from a caller's own "fp32" by
+    identity, so bf16 tables given with no ``row_dtype`` imply the bf16 path while an explicit
+    "fp32" beside them is an error."""
+
+
+_FP32 = _Default("fp32")
+
+
+def _bf16_rows(user_emb: torch.Tensor, post_emb: torch.Tensor, row_dtype: str, what: str) -> bool:
+    """Whether the call scores bf16 rows: ``row_dtype="bf16"``, or bf16 tables."""
+    mode = ops._row_dtype_value(row_dtype, "row_dtype")
+    dts = (user_emb.dtype, post_emb.dtype)
+    if dts == (torch.bfloat16, torch.bfloat16):
+        if mode == "fp32" and row_dtype is not _FP32:
+            raise TypeError(f"{what}: bf16 embeddings with row_dtype='fp32'")
+        return True
+    if dts != (torch.float32, torch.float32):
+        raise TypeError(f"{what}: fp32 embeddings (the reference dtype) or, for the bf16 rows, "
+                        f"both tables in bf16 expected; got {dts[0]} and {dts[1]}")
+    return mode == "bf16"
+
+
+def _as_bf16(t: torch.Tensor) -> torch.Tensor:
+    return t.contiguous() if t.dtype == torch.bfloat16 else ops.rows_to_bf16(t)
+
+
 def _fused_ok(d: int, fused: Optional[bool]) -> bool:
     if fused is None:
         return d in (64, 128)
@@ -54,7 +86,8 @@ def _fused_ok(d: int, fused: Optional[bool]) -> bool:
 
 def evaluate(test_edges: torch.Tensor, user_emb: torch.Tensor, post_emb: torch.Tensor,
              K: int = 10, num_users: Optional[int] = None,
-             batch_scores: int = 1 << 30, fused: Optional[bool] = None) -> Tuple[float, float]:
+             batch_scores: int = 1 << 30, fused: Optional[bool] = None,
+             row_dtype: str = _FP32) -> Tuple[float, float]:
     """Mean Recall@K and NDCG@K over the test users (train_gnn.py:289-367).
 
     ``test_edges``: [2, E] user -> global post id (post ids offset by ``num_users``, as the
@@ -62,10 +95,15 @@ def evaluate(test_edges: torch.Tensor, user_emb: torch.Tensor, post_emb: torch.T
     ``batch_scores`` bounds the floats of one materialised score matrix (rows x candidates).
     ``fused`` (default: when d is 64 or 128) scores and ranks in one kernel without materialising
     the scores (hgnn_score_topk); rows whose K-th score ties the next one are redone on the
-    materialised path, which sklearn's tie groups need."""
+    materialised path, which sklearn's tie groups need.
+    ``row_dtype``: "fp32" (the default whatever ``ops.ROW_DTYPE`` says: the reference-parity
+    path) or "bf16"; ``torch.bfloat16`` tables imply "bf16".  The bf16 mode rounds the rows that
+    are scored (the test users' and the candidates') to bf16, R(T) = T.to(bfloat16).float(), and
+    returns what the fp32 path returns on R(U), R(P): the fused kernel reads the bf16 rows
+    themselves (hgnn_score_topk_bf16), the materialised path (tie redo, other widths) their fp32
+    widening."""
+    bf16 = _bf16_rows(user_emb, post_emb, row_dtype, "evaluate")
     dev = N.require_device(user_emb, post_emb, test_edges)
-    if user_emb.dtype != torch.float32 or post_emb.dtype != torch.float32:
-        raise TypeError("evaluate: fp32 embeddings expected (the reference dtype)")
     nu = int(user_emb.shape[0]) if num_users is None else int(num_users)
     g = _Grouped(test_edges, nu, int(post_emb.shape[0]))
     n_rows, C = int(g.users.numel()), int(g.cand.numel())
@@ -79,16 +117,26 @@ def evaluate(test_edges: torch.Tensor, user_emb: torch.Tensor, post_emb: torch.T
     ndcg = torch.empty(n_rows, dtype=torch.float64, device=dev)
     lib = N.lib()
     users32 = g.users.to(torch.int32)
+    if bf16:
+        # only the scored rows are cast: row r of U_b is test user r's, P_b the padded candidates
+        U_b = _as_bf16(user_emb.index_select(0, g.users))
+        P_b = _as_bf16(P_c)
+        P_c = None                                         # the materialised path widens P_b
     if _fused_ok(d, fused):
         k = min(K, C)
         L = k + 1 if C > k else k
-        U = user_emb.contiguous()
         topv = torch.empty(n_rows, L, dtype=torch.float32, device=dev)
         topi = torch.empty(n_rows, L, dtype=torch.int32, device=dev)
         tie = torch.empty(n_rows, dtype=torch.int32, device=dev)
-        N.check(lib.hgnn_score_topk(N.ptr(U), N.ptr(users32), n_rows, N.ptr(P_c), C, d, L,
-                                    N.ptr(topv), N.ptr(topi), N.stream_ptr(dev)),
-                "hgnn_score_topk")
+        if bf16:
+            N.check(lib.hgnn_score_topk_bf16(N.ptr(U_b), None, n_rows, N.ptr(P_b), C, d, L,
+                                             N.ptr(topv), N.ptr(topi), N.stream_ptr(dev)),
+                    "hgnn_score_topk_bf16")
+        else:
+            U = user_emb.contiguous()
+            N.check(lib.hgnn_score_topk(N.ptr(U), N.ptr(users32), n_rows, N.ptr(P_c), C, d, L,
+                                        N.ptr(topv), N.ptr(topi), N.stream_ptr(dev)),
+                    "hgnn_score_topk")
         N.check(lib.hgnn_topk_finish(N.ptr(topv), N.ptr(topi), n_rows, L, C, K, N.ptr(g.rowptr),
                                      N.ptr(g.true_cand), N.ptr(g.true_count), N.ptr(recall),
                                      N.ptr(ndcg), N.ptr(tie), N.stream_ptr(dev)),
@@ -98,6 +146,8 @@ def evaluate(test_edges: torch.Tensor, user_emb: torch.Tensor, post_emb: torch.T
     else:
         redo, n_redo = None, n_rows                        # every row on the materialised path
     if n_redo:
+        if bf16:
+            P_c = P_b.float()
         rows = max(1, min(n_redo, batch_scores // ld))
         buf = torch.empty(rows, ld, dtype=torch.float32, device=dev)
         for r0 in range(0, n_redo, rows):
@@ -105,7 +155,9 @@ def evaluate(test_edges: torch.Tensor, user_emb: torch.Tensor, post_emb: torch.T
             S = buf[: r1 - r0]                             # columns >= C (padding) are ignored
             rmap = (torch.arange(r0, r1, dtype=torch.int32, device=dev) if redo is None
                     else redo[r0:r1])
-            torch.mm(user_emb.index_select(0, users32[rmap.long()]), P_c.T, out=S)
+            U_r = (U_b.index_select(0, rmap.long()).float() if bf16
+                   else user_emb.index_select(0, users32[rmap.long()]))
+            torch.mm(U_r, P_c.T, out=S)
             N.check(lib.hgnn_topk_metrics_rows(
                 N.ptr(S), r1 - r0, C, ld, N.ptr(rmap), N.ptr(g.rowptr), N.ptr(g.true_cand),
                 N.ptr(g.true_count), K, None, N.ptr(recall), N.ptr(ndcg), N.stream_ptr(dev)),
@@ -130,16 +182,18 @@ def topk_metrics(scores: torch.Tensor, true_rowptr: torch.Tensor, true_cand: tor
 
 
 def recommend(user_emb: torch.Tensor, post_emb: torch.Tensor, K: int = 10,
-              batch_scores: int = 1 << 30,
-              fused: Optional[bool] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+              batch_scores: int = 1 << 30, fused: Optional[bool] = None,
+              row_dtype: str = _FP32) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-K posts for every user row: ``(topk_scores, topk_indices)``, each ``[n_users, k]``,
     k = min(K, n_posts) — the scoring of ``recommend_for_user_inductive`` (inference.py:427-429:
     ``torch.topk(user_emb @ known_post_emb.T, min(K, len(scores)))``) for a whole batch of users
     at once.  Scores descend; equal scores list the lower post index first.  ``fused`` (default
-    for d in (64, 128), K <= 64): one kernel, no score matrix."""
+    for d in (64, 128), K <= 64): one kernel, no score matrix.  ``row_dtype`` as in ``evaluate``:
+    "bf16", or ``torch.bfloat16`` tables, ranks the rows rounded to bf16 (the fused kernel on
+    bf16 MFMA; other widths and K > 64 on the materialised path over the widened rows), and the
+    returned scores are fp32 scores of the rounded rows."""
+    bf16 = _bf16_rows(user_emb, post_emb, row_dtype, "recommend")
     dev = N.require_device(user_emb, post_emb)
-    if user_emb.dtype != torch.float32 or post_emb.dtype != torch.float32:
-        raise TypeError("recommend: fp32 embeddings expected (the reference dtype)")
     n, C = int(user_emb.shape[0]), int(post_emb.shape[0])
     if C == 0:
         raise ValueError("recommend: no posts to rank")
@@ -150,11 +204,20 @@ def recommend(user_emb: torch.Tensor, post_emb: torch.Tensor, K: int = 10,
     if n == 0:
         return out_s, out_i.long()
     lib = N.lib()
+    if bf16:
+        user_emb, post_emb = _as_bf16(user_emb), _as_bf16(post_emb)
     if _fused_ok(d, fused) and k <= 64:
+        if bf16:
+            N.check(lib.hgnn_score_topk_bf16(N.ptr(user_emb), None, n, N.ptr(post_emb), C, d, k,
+                                             N.ptr(out_s), N.ptr(out_i), N.stream_ptr(dev)),
+                    "hgnn_score_topk_bf16")
+            return out_s, out_i.long()
         N.check(lib.hgnn_score_topk(N.ptr(user_emb.contiguous()), None, n,
                                     N.ptr(post_emb.contiguous()), C, d, k, N.ptr(out_s),
                                     N.ptr(out_i), N.stream_ptr(dev)), "hgnn_score_topk")
         return out_s, out_i.long()
+    if bf16:
+        user_emb, post_emb = user_emb.float(), post_emb.float()   # R(U), R(P)
     ld = (C + 3) // 4 * 4
     P_c = post_emb.new_zeros(ld, d)
     P_c[:C] = post_emb
