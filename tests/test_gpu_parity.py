@@ -1329,6 +1329,65 @@ def test_linear_multi_equals_per_job_calls(case):
                 assert float((a - r).abs().max()) <= tol, (float((a - r).abs().max()), tol)
 
 
+def test_sampled_block_layer_is_bitwise_on_both_k2_routes(monkeypatch):
+    """A sampled-block layer (two groups with ``n_root``: 100 of 300 users and 20 of 40 posts
+    are roots; user<-post, user<-user, post<-user; d = h = 64; every input needs its gradient,
+    so both types are K2 targets holding a root prefix) run twice.  As is: one multi K1 launch,
+    the root gradients in unzeroed buffers, and the K2s as rounds whose first adds below each
+    prefix and writes the rows after it.  Under a kernel timer the multi gathers are off: one
+    gather per relation into zero-filled buffers.  K3 takes the same entry both times, and a
+    multi gather is bitwise its single calls (test_gather_multi_equals_single_calls), so the
+    outputs and every gradient are bitwise equal."""
+    gen = torch.Generator().manual_seed(23)
+    nu, npost, ru, rp, d, h = 300, 40, 100, 20, 64, 64
+
+    def rel(n_src, n_dst):      # short rows, some empty; no heavy row either way
+        deg = torch.randint(0, 7, (n_dst,), generator=gen)
+        rowptr = torch.zeros(n_dst + 1, dtype=torch.int32)
+        rowptr[1:] = torch.cumsum(deg, 0)
+        col = torch.randint(0, n_src, (int(rowptr[-1]),), generator=gen, dtype=torch.int32)
+        return graph.RelationCSR.from_csr(rowptr.to(DEV), col.to(DEV), n_src, n_dst,
+                                          may_have_heavy_rows=False)
+
+    groups = (ops.DstGroup("user", (("post", rel(npost, ru)), ("user", rel(nu, ru))), True, True,
+                           (), n_root=ru),
+              ops.DstGroup("post", (("user", rel(nu, rp)),), True, True, (), n_root=rp))
+    spec = ops.LayerSpec(("post", "user"), groups)
+    x0 = {"user": torch.randn(nu, d, generator=gen), "post": torch.randn(npost, d, generator=gen)}
+    w0 = [(0.1 * torch.randn(h, 3 * d, generator=gen), torch.randn(h, generator=gen)),
+          (0.1 * torch.randn(h, 2 * d, generator=gen), torch.randn(h, generator=gen))]
+    douts = {"user": torch.randn(ru, h, generator=gen).to(DEV),
+             "post": torch.randn(rp, h, generator=gen).to(DEV)}
+    multi = []
+    real = ops._gather_multi
+    monkeypatch.setattr(ops, "_gather_multi", lambda *a, **k: (multi.append(1), real(*a, **k))[1])
+
+    def run():
+        xs = {t: v.to(DEV).requires_grad_() for t, v in x0.items()}
+        ws = [(w.to(DEV).requires_grad_(), b.to(DEV).requires_grad_()) for w, b in w0]
+        out = ops.hetero_layer(spec, xs, ws)
+        torch.autograd.backward([out["user"], out["post"]], [douts["user"], douts["post"]])
+        res = {"out." + t: out[t].detach() for t in out}
+        res.update({"dx." + t: xs[t].grad for t in xs})
+        for i, (w, b) in enumerate(ws):
+            res[f"dw{i}"], res[f"db{i}"] = w.grad, b.grad
+        return res
+
+    batched = run()
+    assert len(multi) == 2              # the three K1s; K2 round 0 (round 1 is one relation)
+    try:
+        ops.set_timer(ops.KernelTimer())
+        single = run()
+    finally:
+        ops.set_timer(None)
+    assert len(multi) == 2              # none under the timer
+    assert set(batched) == set(single) and len(batched) == 8
+    for k in batched:
+        assert batched[k].shape == single[k].shape and torch.equal(batched[k], single[k]), k
+    assert tuple(batched["dx.user"].shape) == (nu, d)
+    assert tuple(batched["out.user"].shape) == (ru, h)
+
+
 @pytest.mark.parametrize("wd", [0.0, 0.01])
 def test_adam_matches_torch(wd):
     """optim.Adam (hgnn_adam_multi: every parameter in one launch, the step count on the device)

@@ -14,11 +14,10 @@ gradient sums the reference's autograd would do with separate add kernels happen
 """
 from __future__ import annotations
 
-import contextlib
 import dataclasses
 import os
 import weakref
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -569,17 +568,14 @@ def relu_mask_for(n: int, h: int, relu: bool, dev, k: Optional[int] = None
                   ) -> Optional[torch.Tensor]:
     """The bit form of a K3 output's ReLU mask (``hgnn_linear_fwd_mask``: 16 B per row, the
     backward reads it instead of the 4h-byte output), or None where the kernels have no bit form
-    (no ReLU, h not a multiple of 16 or above 128, or ``HGNN_RELU_BITS=0``) or where no kernel
-    would read it: an input width ``k`` outside the persistent kernels' {64, 128, 256} (the
-    general kernels read the output, and the bits would cost a separate launch)."""
-    if not (RELU_BITS and relu and h % 16 == 0 and h <= 128):
+    (no ReLU, h not a multiple of 16 or above 128) or where no kernel would read it: an input
+    width ``k`` outside the persistent kernels' {64, 128, 256} (the general kernels read the
+    output, and the bits would cost a separate launch)."""
+    if not (relu and h % 16 == 0 and h <= 128):
         return None
     if k is not None and k not in (64, 128, 256):
         return None
     return torch.empty((n, 4), dtype=torch.int32, device=dev)
-
-
-RELU_BITS = os.environ.get("HGNN_RELU_BITS", "1") == "1"
 
 
 def _check_rows(segs, n, what):
@@ -680,39 +676,67 @@ def linear_bwd(segs, w, dout, out_act, dxs: Sequence[Optional[torch.Tensor]], ne
     return dw, db
 
 
+class FwdJob(NamedTuple):
+    """One K3 forward of :func:`linear_fwd_many`."""
+    segs: Sequence[torch.Tensor]
+    w: torch.Tensor
+    b: Optional[torch.Tensor]
+    relu: bool
+    mask: Optional[torch.Tensor]          # relu_mask_for's buffer: receives the ReLU bits
+
+
+class BwdJob(NamedTuple):
+    """One K3 backward of :func:`linear_bwd_many`."""
+    segs: Sequence[torch.Tensor]
+    w: torch.Tensor
+    dout: torch.Tensor
+    out_act: Optional[torch.Tensor]       # the forward's output where it went through a ReLU
+    dxs: Sequence[Optional[torch.Tensor]]
+    need_w: bool
+    need_b: bool
+    mask: Optional[torch.Tensor]          # the forward's ReLU bits
+
+
 def linear_fwd_many(jobs) -> List[torch.Tensor]:
-    """:func:`linear_fwd` (no ``add``) of each ``(segs, w, b, relu, mask_out)`` job in one native
-    call (``hgnn_linear_fwd_multi``): a sampled layer's two destination types on the K = 384 /
-    512 split path share each column block's launch; anything else runs job by job there."""
-    if len(jobs) == 1 or len({int(j[1].shape[0]) for j in jobs}) > 1:   # (one output width)
-        return [linear_fwd(segs, w, b, relu, mask_out=mk) for segs, w, b, relu, mk in jobs]
-    info = [_lin_fwd_job("linear_fwd_many", segs, w, b, mask_out=mk) for segs, w, b, _, mk in jobs]
+    """:func:`linear_fwd` (no ``add``) of each :class:`FwdJob` (or plain tuple in its field
+    order) in one native call (``hgnn_linear_fwd_multi``): a sampled layer's two destination
+    types on the K = 384 / 512 split path share each column block's launch; anything else runs
+    job by job there."""
+    jobs = [FwdJob(*j) for j in jobs]
+    if len(jobs) == 1 or len({int(j.w.shape[0]) for j in jobs}) > 1:   # (one output width)
+        return [linear_fwd(j.segs, j.w, j.b, j.relu, mask_out=j.mask) for j in jobs]
+    info = [_lin_fwd_job("linear_fwd_many", j.segs, j.w, j.b, mask_out=j.mask) for j in jobs]
     rows, outs = [i[0] for i in info], [i[3] for i in info]
     ks = [k for i in info for k in i[2]]
-    dev, h = jobs[0][1].device, info[0][1]
+    dev, h = jobs[0].w.device, info[0][1]
     with _timed(f"linear_fwd_multi[{'+'.join(str(r) for r in rows)}x{sum(ks) // len(jobs)}->{h}]",
                 sum(i[4] for i in info), flops=sum(i[5] for i in info)):
         N.check(N.lib().hgnn_linear_fwd_multi(
-            len(jobs), N.int_array([len(j[0]) for j in jobs]),
-            N.ptr_array([s_ for j in jobs for s_ in j[0]]), N.int_array(ks), N.i64_array(rows),
-            N.ptr_array([j[1] for j in jobs]), h, N.ptr_array([j[2] for j in jobs]),
-            N.int_array([1 if j[3] else 0 for j in jobs]), N.ptr_array(outs),
-            N.ptr_array([j[4] for j in jobs]), N.stream_ptr(dev)), "hgnn_linear_fwd_multi")
+            len(jobs), N.int_array([len(j.segs) for j in jobs]),
+            N.ptr_array([s_ for j in jobs for s_ in j.segs]), N.int_array(ks), N.i64_array(rows),
+            N.ptr_array([j.w for j in jobs]), h, N.ptr_array([j.b for j in jobs]),
+            N.int_array([1 if j.relu else 0 for j in jobs]), N.ptr_array(outs),
+            N.ptr_array([j.mask for j in jobs]), N.stream_ptr(dev)), "hgnn_linear_fwd_multi")
     return outs
 
 
+def _linear_bwd_of(j: BwdJob):
+    """:func:`linear_bwd` of one job."""
+    return linear_bwd(j.segs, j.w, j.dout, j.out_act, j.dxs, j.need_w, j.need_b, mask=j.mask)
+
+
 def linear_bwd_many(jobs):
-    """:func:`linear_bwd` (no ``dz_out``, no ``dx_add``) of each ``(segs, w, dout, out_act, dxs,
-    need_w, need_b, mask)`` job in one native call (``hgnn_linear_bwd_multi``); returns the
-    ``(dw, db)`` of each."""
-    if len(jobs) == 1 or len({int(j[1].shape[0]) for j in jobs}) > 1:
-        return [linear_bwd(segs, w, dout, out_act, dxs, need_w, need_b, mask=mk)
-                for segs, w, dout, out_act, dxs, need_w, need_b, mk in jobs]
-    info = [_lin_bwd_job("linear_bwd_many", segs, w, dout, out_act, dxs, need_w, need_b, mask=mk)
-            for segs, w, dout, out_act, dxs, need_w, need_b, mk in jobs]
+    """:func:`linear_bwd` (no ``dz_out``, no ``dx_add``) of each :class:`BwdJob` (or plain tuple
+    in its field order) in one native call (``hgnn_linear_bwd_multi``); returns the ``(dw, db)``
+    of each."""
+    jobs = [BwdJob(*j) for j in jobs]
+    if len(jobs) == 1 or len({int(j.w.shape[0]) for j in jobs}) > 1:
+        return [_linear_bwd_of(j) for j in jobs]
+    info = [_lin_bwd_job("linear_bwd_many", j.segs, j.w, j.dout, j.out_act, j.dxs, j.need_w,
+                         j.need_b, mask=j.mask) for j in jobs]
     rows, kt = [i[0] for i in info], [sum(i[2]) for i in info]
     dws, dbs = [i[3] for i in info], [i[4] for i in info]
-    dev, h = jobs[0][1].device, info[0][1]
+    dev, h = jobs[0].w.device, info[0][1]
     ws = None
     if any(d is not None for d in dws + dbs):
         ws = N.workspace(N.lib().hgnn_linear_bwd_multi_ws_bytes(
@@ -720,13 +744,13 @@ def linear_bwd_many(jobs):
     with _timed(f"linear_bwd_multi[{'+'.join(str(r) for r in rows)}x{sum(kt) // len(jobs)}->{h}]",
                 sum(i[6] for i in info), flops=sum(i[7] for i in info)):
         N.check(N.lib().hgnn_linear_bwd_multi(
-            len(jobs), N.int_array([len(j[0]) for j in jobs]),
-            N.ptr_array([s_ for j in jobs for s_ in j[0]]),
+            len(jobs), N.int_array([len(j.segs) for j in jobs]),
+            N.ptr_array([s_ for j in jobs for s_ in j.segs]),
             N.int_array([k for i in info for k in i[2]]), N.i64_array(rows),
-            N.ptr_array([j[1] for j in jobs]), h, N.ptr_array([j[2] for j in jobs]),
-            N.ptr_array([j[3] for j in jobs]),
-            N.ptr_array([j[7] if j[3] is not None else None for j in jobs]),
-            N.ptr_array([d for j in jobs for d in j[4]]), None, N.ptr_array(dws),
+            N.ptr_array([j.w for j in jobs]), h, N.ptr_array([j.dout for j in jobs]),
+            N.ptr_array([j.out_act for j in jobs]),
+            N.ptr_array([j.mask if j.out_act is not None else None for j in jobs]),
+            N.ptr_array([d for j in jobs for d in j.dxs]), None, N.ptr_array(dws),
             N.ptr_array(dbs), N.ptr(ws), 0 if ws is None else ws.numel(), N.stream_ptr(dev)),
             "hgnn_linear_bwd_multi")
     return list(zip(dws, dbs))
@@ -987,40 +1011,6 @@ class DstGroup:
     static: Tuple[bool, ...] = ()
 
 
-def _is_static(g: DstGroup, i: int) -> bool:
-    """Relation i of the group reads a table its caller declared static (never a pre-projected
-    relation: that one gathers the projected rows, which change with the weights)."""
-    return bool(i < len(g.static) and g.static[i] and not (i < len(g.pre) and g.pre[i]))
-
-
-def _root_type(g: DstGroup) -> str:
-    return g.dst if g.root_src is None else g.root_src
-
-
-def _root(g: DstGroup, xs) -> torch.Tensor:
-    """The destination rows' own features (the root segment): a prefix view in a block."""
-    if g.root_src is not None:
-        return xs[g.root_src]
-    x = xs[g.dst]
-    return x if g.n_root is None else x[:g.n_root]
-
-
-def _root_grad_buffer(g: DstGroup, xs, gx, prefix=None) -> torch.Tensor:
-    """Allocates gx[dst] and returns the view the root segment's dgrad writes (a block's prefix;
-    the rows after it are zero until the K2s add into them — or, with ``prefix`` (a dict), left
-    unwritten and recorded there: the first K2 round writes them fresh, ``_k2_rounds``)."""
-    x = xs[_root_type(g)]
-    if g.n_root is None or g.root_src is not None:
-        gx[_root_type(g)] = torch.empty_like(x)
-        return gx[_root_type(g)]
-    if prefix is not None:
-        gx[g.dst] = torch.empty_like(x)
-        prefix[g.dst] = int(g.n_root)
-    else:
-        gx[g.dst] = torch.zeros_like(x)
-    return gx[g.dst][:g.n_root]
-
-
 PRE_PROJECTION = os.environ.get("HGNN_PREPROJECT", "1") == "1"
 
 
@@ -1050,257 +1040,292 @@ class LayerSpec:
     types: Tuple[str, ...]                       # order of node-feature inputs
     groups: Tuple[DstGroup, ...]
     # storage of the rows the layer's forward gathers: "fp32", "bf16", or None for ops.ROW_DTYPE
-    # at call time (see ``_rounds``)
+    # at call time (see ``_layer_plan``)
     row_dtype: Optional[str] = None
 
 
-def _rounds(g: DstGroup, i: int, width: int) -> bool:
-    """bf16 row mode: whether relation i of the group gathers the bf16 copy of its table (of
-    ``width`` columns: the source table, or the projected rows of a pre-projected relation).
-    Only a full-table group's relations do (a sampled block — ``n_root`` / ``root_src`` — keeps
-    fp32 rows), never one whose table the caller declared static (a model input is gathered once
-    and kept, whatever HGNN_STATIC_AGG says), and only at a width that is a multiple of 8."""
-    if g.n_root is not None or g.root_src is not None or width % 8 != 0:
-        return False
-    pre = i < len(g.pre) and g.pre[i]
-    return bool(pre or not (i < len(g.static) and g.static[i]))
+# ----------------------------------------------------------------------------- layer plan
+class _GroupPlan(NamedTuple):
+    """What one destination group of a layer call does, every per-relation tuple normalised to
+    one entry per relation."""
+    dst: str
+    rels: Tuple[Tuple[str, RelationCSR], ...]
+    relu: bool
+    root: bool                      # the destination rows' own features are a segment
+    root_type: str                  # the input holding them
+    prefix: Optional[int]           # they are its first ``prefix`` rows (a block); None: all
+    n_dst: int                      # destination rows
+    # relation i's lin_l runs on the source table and the projected rows are gathered
+    pre: Tuple[bool, ...]
+    # relation i's aggregate is kept across calls (never a pre-projected relation: that one
+    # gathers the projected rows, which change with the weights)
+    static: Tuple[bool, ...]
+    bf16: Tuple[bool, ...]          # relation i gathers the bf16 copy of its table
+    cols: Tuple[Tuple[int, int], ...]   # (offset, width) of relation i's lin_l block in the weight
+    root_col: int                   # offset of the root block (the weight's last)
+    main: Tuple[int, ...]           # the relations that are not pre-projected: the K3 segments
 
 
-class _Lanes:
-    """Two in-order HIP streams (the caller's current stream + one side stream per device) for
-    independent kernel chains.  Every tensor that escapes a side-stream chain is allocated on the
-    main stream beforehand or record_stream()'d for it, and the main stream joins the side
-    stream before returning, so the caching allocator never hands out memory still in use.
-    Off by default: on cfg2 every overlapped pair slowed each other by as much as the overlap
-    saved (layers: 10.55 vs 10.51 ms/step, the gathers already saturate the memory system; loss:
-    the sort beside pass A stretched 0.49 -> 1.66 ms — pass A's workgroups hold every CU, so the
-    sort's only get dispatched as it drains).  HGNN_STREAMS=1 turns it on."""
+class _LayerPlan(NamedTuple):
+    types: Tuple[str, ...]          # order of the node-feature inputs
+    groups: Tuple[_GroupPlan, ...]
+    # no group has a pre-projected relation: one K1 stage and one multi K3 call each way for the
+    # layer.  Otherwise every group runs its own kernels one after the other.
+    batched: bool
+    shadow: Tuple[str, ...]         # source types gathered from a bf16 copy, in cast order
 
-    _side: Dict[torch.device, torch.cuda.Stream] = {}
-    enabled = os.environ.get("HGNN_STREAMS", "0") == "1"
 
-    def __init__(self, dev: torch.device, n_chains: int, force: bool = False):
-        self.main = self.side = None
-        if (self.enabled or force) and n_chains > 1:
-            self.main = torch.cuda.current_stream(dev)
-            self.side = _Lanes._side.get(dev)
-            if self.side is None:
-                self.side = _Lanes._side[dev] = torch.cuda.Stream(dev)
-            self.side.wait_stream(self.main)
+def _layer_plan(spec: LayerSpec, shapes: Dict[str, Tuple[int, int]], hidden: Sequence[int],
+                bf16: bool) -> _LayerPlan:
+    """Every decision of one ``hetero_layer`` call, from the spec, the inputs' ``(rows,
+    columns)`` by type, each group's output width and the resolved row mode; no tensor is read.
 
-    def ctx(self, i: int):
-        """The stream context of chain i: a no-op with one lane (no Stream objects built — at a
-        few hundred per sampled mini-batch step they were a visible share of its host time)."""
-        if self.side is None:
-            return contextlib.nullcontext()
-        return torch.cuda.stream(self.side if i % 2 == 1 else self.main)
+    bf16 row mode: a relation gathers the bf16 copy of its table (the source table, or the
+    projected rows of a pre-projected relation, so judged at the output width) only in a
+    full-table group (a sampled block — ``n_root`` / ``root_src`` — keeps fp32 rows), never
+    where the caller declared the table static (a model input is gathered once and kept,
+    whatever HGNN_STATIC_AGG says), and only at a width that is a multiple of 8."""
+    groups, shadow = [], []
+    for gi, g in enumerate(spec.groups):
+        block = g.n_root is not None or g.root_src is not None
+        if any(g.static) and block:
+            # a block's tables are buffers native kernels refill through raw pointers (no
+            # version bump): an aggregate kept from them would be replayed stale
+            raise ValueError("hetero_layer: a sampled block's relations are never static")
+        R = range(len(g.rels))
+        pre = tuple(bool(i < len(g.pre) and g.pre[i]) for i in R)
+        if g.root_src is not None and (any(pre) or g.n_root is not None or not g.root):
+            raise ValueError("hetero_layer: root_src takes a root segment, no n_root and no "
+                             "pre-projected relation")
+        root_type = g.dst if g.root_src is None else g.root_src
+        n_dst = int(shapes[root_type][0] if g.n_root is None else g.n_root)
+        for src, csr in g.rels:
+            if csr.n_dst != n_dst or csr.n_src != shapes[src][0]:
+                raise ValueError(f"hetero_layer: relation {src}->{g.dst} is {csr.n_src}->"
+                                 f"{csr.n_dst} rows, the tables give {shapes[src][0]}->{n_dst}")
+        static = tuple(bool(i < len(g.static) and g.static[i] and not pre[i]) for i in R)
+        cols, o = [], 0
+        for src, _ in g.rels:
+            cols.append((o, int(shapes[src][1])))
+            o += cols[-1][1]
+        rounds = tuple(bool(bf16 and not block and not static[i]
+                            and (hidden[gi] if pre[i] else cols[i][1]) % 8 == 0) for i in R)
+        shadow += [g.rels[i][0] for i in R
+                   if rounds[i] and not pre[i] and g.rels[i][0] not in shadow]
+        groups.append(_GroupPlan(g.dst, tuple(g.rels), bool(g.relu), bool(g.root), root_type,
+                                 g.n_root, n_dst, pre, static, rounds, tuple(cols), o,
+                                 tuple(i for i in R if not pre[i])))
+    return _LayerPlan(tuple(spec.types), tuple(groups), not any(any(p.pre) for p in groups),
+                      tuple(shadow))
 
-    def escape(self, i: int, *tensors):
-        if self.side is not None and i % 2 == 1:
-            for t in tensors:
-                if t is not None:
-                    t.record_stream(self.main)
 
-    def join(self):
-        if self.side is not None:
-            self.main.wait_stream(self.side)
+def _fresh_prefix(plan: _LayerPlan, gi: int, need_x: Dict[str, bool], k2_targets
+                  ) -> Optional[int]:
+    """Backward: group ``gi``'s root gradient goes into an unzeroed buffer of its input type —
+    returns the number of rows the K3 dgrad writes (the block's roots) — or None: the buffer is
+    zero-filled.  Fresh only in a batched layer, for a block given by ``n_root``, when K2s will
+    add into that type (``k2_targets``): the first K2 round then adds into the prefix and writes
+    the rows after it (``_k2_rounds``).  A block without roots is never fresh: the kernel's
+    limit of 0 means "accumulate into every row", which would read the unwritten buffer."""
+    p = plan.groups[gi]
+    if not (plan.batched and p.root and p.prefix is not None and need_x[p.root_type]
+            and p.root_type in k2_targets):
+        return None
+    return p.prefix if p.prefix > 0 else None
+
+
+def _root(p: _GroupPlan, t: torch.Tensor) -> torch.Tensor:
+    """The group's destination rows of ``t``, a tensor shaped like its root input (the features:
+    the root segment; their gradient: what its dgrad writes): a prefix view in a block."""
+    return t if p.prefix is None else t[:p.prefix]
+
+
+def _main_weight(p: _GroupPlan, w: torch.Tensor) -> torch.Tensor:
+    """The fused weight without the pre-projected relations' lin_l blocks."""
+    if not any(p.pre):
+        return w.contiguous()
+    keep = [w[:, o:o + k] for o, k in (p.cols[i] for i in p.main)]
+    if p.root:
+        keep.append(w[:, p.root_col:])
+    return torch.cat(keep, dim=1).contiguous()
+
+
+def _fwd_job(p: _GroupPlan, xs, aggrs, w, b) -> FwdJob:
+    """The K3 forward of a group over its main aggregates (+ root rows), with its mask buffer."""
+    segs = list(aggrs) + ([_root(p, xs[p.root_type])] if p.root else [])
+    mask = relu_mask_for(p.n_dst, int(w.shape[0]), p.relu, w.device,
+                         sum(int(t.shape[1]) for t in segs))
+    return FwdJob(segs, _main_weight(p, w), None if b is None else b.contiguous(), p.relu, mask)
+
+
+def _main_dxs(p: _GroupPlan, aggrs, need_x, pending) -> List[Optional[torch.Tensor]]:
+    """The gradient buffer of each main aggregate (None where no source gradient comes of it),
+    each queued in ``pending`` for the K2 into its source type."""
+    dxs: List[Optional[torch.Tensor]] = []
+    for i, a in zip(p.main, aggrs):
+        src, csr = p.rels[i]
+        if need_x[src] and csr.num_edges > 0:
+            dxs.append(torch.empty_like(a))
+            pending.setdefault(src, []).append((dxs[-1], csr))
+        else:
+            dxs.append(None)
+    return dxs
 
 
 class _HeteroLayer(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, spec: LayerSpec, *flat):
-        nt = len(spec.types)
-        xs = dict(zip(spec.types, flat[:nt]))
+    def forward(ctx, plan: _LayerPlan, *flat):
+        nt = len(plan.types)
+        xs = dict(zip(plan.types, flat[:nt]))
         wb = flat[nt:]
-        ng = len(spec.groups)
-        outs, aggrs_by_g, masks = [None] * ng, [None] * ng, [None] * ng
-        dev = flat[0].device
         # bf16 row mode: one bf16 copy per distinct source table some relation of the layer
-        # gathers (``_rounds``), cast here on the caller's stream before the lanes fork and held
-        # until the forward returns.  Nothing is saved from them: the backward is the fp32 one,
-        # evaluated at the aggregates computed from the rounded rows.
-        bf16 = resolve_row_dtype(spec.row_dtype) == "bf16"
-        shadow: Dict[str, torch.Tensor] = {}
-        if bf16:
-            for g in spec.groups:
-                for i, (src, _) in enumerate(g.rels):
-                    if (src not in shadow and not (i < len(g.pre) and g.pre[i])
-                            and _rounds(g, i, int(xs[src].shape[1]))):
-                        shadow[src] = rows_to_bf16(xs[src])
+        # gathers, cast before any gather and held until the forward returns.  Nothing is saved
+        # from them: the backward is the fp32 one, evaluated at the aggregates computed from the
+        # rounded rows.
+        shadow = {src: rows_to_bf16(xs[src]) for src in plan.shadow}
 
-        def k1(g, i, src, csr):
-            if src in shadow and _rounds(g, i, int(xs[src].shape[1])):
+        def k1(p, i):
+            src, csr = p.rels[i]
+            if p.bf16[i]:
                 return gather_mean(shadow[src], csr)
-            return gather_mean(xs[src], csr, static=_is_static(g, i), name=f"{src}->{g.dst}")
+            return gather_mean(xs[src], csr, static=p.static[i], name=f"{src}->{p.dst}")
 
-        lanes = _Lanes(dev, ng)
-        many = None
-        if lanes.side is None and not any(any(g.pre) for g in spec.groups):
+        def k1_group(p, w):
+            """One group's gathers, relation by relation: its main aggregates, and the means of
+            its pre-projected relations' P = x_src W_r^T summed into one [N_dst, h] input that
+            the destination update adds in its epilogue."""
+            aggrs, add = [], None
+            for i, (src, csr) in enumerate(p.rels):
+                if p.pre[i]:
+                    o, k = p.cols[i]
+                    P = linear_fwd([xs[src]], w[:, o:o + k].contiguous(), None, False)
+                    if p.bf16[i]:
+                        P = rows_to_bf16(P)    # rounded after the projection: the table the
+                                               # gather reads
+                    add = gather_mean(P, csr, out=add)
+                    del P
+                else:
+                    aggrs.append(k1(p, i))
+            return aggrs, add
+
+        if plan.batched:
             if shadow:
-                many = iter([k1(g, i, src, csr) for g in spec.groups
-                             for i, (src, csr) in enumerate(g.rels)])
+                aggrs_by_g = [k1_group(p, None)[0] for p in plan.groups]
             else:
                 # every relation's K1 of the layer in one launch (sampled blocks;
                 # gather_mean_many falls back to one launch each where they do not qualify)
                 many = iter(gather_mean_many(
-                    [(xs[src], csr) for g in spec.groups for src, csr in g.rels],
-                    static=[_is_static(g, i) for g in spec.groups for i in range(len(g.rels))],
-                    names=[f"{src}->{g.dst}" for g in spec.groups for src, _ in g.rels]))
-        if many is not None:
+                    [(xs[src], csr) for p in plan.groups for src, csr in p.rels],
+                    static=[s for p in plan.groups for s in p.static],
+                    names=[f"{src}->{p.dst}" for p in plan.groups for src, _ in p.rels]))
+                aggrs_by_g = [[next(many) for _ in p.rels] for p in plan.groups]
             # and every destination type's K3 in one native call (the split path's column blocks
             # one launch for both types, hgnn_linear_fwd_multi)
-            jobs = []
-            for gi, g in enumerate(spec.groups):
-                w, b = wb[2 * gi], wb[2 * gi + 1]
-                aggrs = [next(many) for _ in g.rels]
-                segs = aggrs + ([_root(g, xs)] if g.root else [])
-                mk = relu_mask_for(segs[0].shape[0], int(w.shape[0]), g.relu, dev,
-                                   sum(int(t.shape[1]) for t in segs))
-                jobs.append((segs, w.contiguous(), None if b is None else b.contiguous(), g.relu,
-                             mk))
-                aggrs_by_g[gi], masks[gi] = aggrs, mk
+            jobs = [_fwd_job(p, xs, aggrs, wb[2 * gi], wb[2 * gi + 1])
+                    for gi, (p, aggrs) in enumerate(zip(plan.groups, aggrs_by_g))]
             outs = linear_fwd_many(jobs)
-        for gi, g in enumerate(spec.groups if many is None else ()):   # independent chains
-            w, b = wb[2 * gi], wb[2 * gi + 1]
-            with lanes.ctx(gi):
-                if any(g.pre):
-                    # pre-projected relations: P = x_src W_r^T, gathered (means summed into
-                    # one [N_dst, h] input) and added in the destination update's epilogue
-                    cols = _group_columns(g, xs)
-                    add, aggrs = None, []
-                    for i, ((src, csr), pre, (o, k)) in enumerate(zip(g.rels, g.pre, cols)):
-                        if pre:
-                            P = linear_fwd([xs[src]], w[:, o:o + k].contiguous(), None, False)
-                            if bf16 and _rounds(g, i, int(P.shape[1])):
-                                P = rows_to_bf16(P)    # rounded after the projection: the
-                                                       # table the gather reads
-                            add = gather_mean(P, csr, out=add)
-                            del P
-                        else:
-                            aggrs.append(k1(g, i, src, csr))
-                    segs = aggrs + ([_root(g, xs)] if g.root else [])
-                    mk = relu_mask_for(_root(g, xs).shape[0], int(w.shape[0]), g.relu, dev,
-                                       sum(int(t.shape[1]) for t in segs))
-                    y = linear_fwd(segs, _main_weight(g, w, cols),
-                                   None if b is None else b.contiguous(), g.relu, add=add,
-                                   mask_out=mk)
-                    del add
-                else:
-                    aggrs = [k1(g, i, src, csr) for i, (src, csr) in enumerate(g.rels)]
-                    segs = aggrs + ([_root(g, xs)] if g.root else [])
-                    mk = relu_mask_for(segs[0].shape[0], int(w.shape[0]), g.relu, dev,
-                                       sum(int(t.shape[1]) for t in segs))
-                    y = linear_fwd(segs, w.contiguous(), None if b is None else b.contiguous(),
-                                   g.relu, mask_out=mk)
-            lanes.escape(gi, y, mk, *aggrs)
-            outs[gi], aggrs_by_g[gi], masks[gi] = y, aggrs, mk
-        lanes.join()
+        else:
+            aggrs_by_g, jobs, outs = [], [], []
+            for gi, p in enumerate(plan.groups):
+                aggrs, add = k1_group(p, wb[2 * gi])
+                j = _fwd_job(p, xs, aggrs, wb[2 * gi], wb[2 * gi + 1])
+                outs.append(linear_fwd(j.segs, j.w, j.b, j.relu, add=add, mask_out=j.mask))
+                del add
+                aggrs_by_g.append(aggrs)
+                jobs.append(j)
         shadow.clear()
-        aggrs_all = [a for aggrs in aggrs_by_g for a in aggrs]
-        ctx.spec = spec
-        ctx.masks = masks          # ReLU bits of each output (None where there is no bit form)
+        ctx.plan = plan
+        ctx.masks = [j.mask for j in jobs]   # ReLU bits of each output (None: no bit form)
         ctx.has_b = [b is not None for b in wb[1::2]]
-        ctx.save_for_backward(*flat[:nt], *[t for t in wb if t is not None], *aggrs_all, *outs)
+        ctx.save_for_backward(*flat[:nt], *[t for t in wb if t is not None],
+                              *[a for aggrs in aggrs_by_g for a in aggrs], *outs)
         return tuple(outs)
 
     @staticmethod
+    def _saved(ctx):
+        """``(xs, [(w, b)], main aggregates by group, outs)`` from what ``forward`` saved."""
+        plan: _LayerPlan = ctx.plan
+        saved = iter(ctx.saved_tensors)
+        xs = {t: next(saved) for t in plan.types}
+        wbs = [(next(saved), next(saved) if hb else None) for hb in ctx.has_b]
+        aggrs_by_g = [[next(saved) for _ in p.main] for p in plan.groups]
+        return xs, wbs, aggrs_by_g, list(saved)
+
+    @staticmethod
     def backward(ctx, *douts):
-        spec: LayerSpec = ctx.spec
-        nt, ng = len(spec.types), len(spec.groups)
-        saved = list(ctx.saved_tensors)
-        xs = dict(zip(spec.types, saved[:nt]))
-        pos = nt
-        wbs = []
-        for hb in ctx.has_b:
-            w = saved[pos]; pos += 1
-            b = None
-            if hb:
-                b = saved[pos]; pos += 1
-            wbs.append((w, b))
-        aggrs_all = saved[pos:pos + sum(_n_main_rels(g) for g in spec.groups)]
-        pos += len(aggrs_all)
-        outs = saved[pos:pos + ng]
+        plan: _LayerPlan = ctx.plan
+        nt, ng = len(plan.types), len(plan.groups)
+        xs, wbs, aggrs_by_g, outs = _HeteroLayer._saved(ctx)
         need = ctx.needs_input_grad[1:]
-        need_x = dict(zip(spec.types, need[:nt]))
-        gx: Dict[str, Optional[torch.Tensor]] = {t: None for t in spec.types}
+        need_x = dict(zip(plan.types, need[:nt]))
+        need_w = [need[nt + 2 * gi] for gi in range(ng)]
+        need_b = [b is not None and need[nt + 2 * gi + 1] for gi, (_, b) in enumerate(wbs)]
+        gx: Dict[str, Optional[torch.Tensor]] = {t: None for t in plan.types}
         gwb: List[Optional[torch.Tensor]] = [None] * (2 * ng)
         pending: Dict[str, list] = {}   # target type -> [(dA, csr)] for K2, after the roots
-        # phase 1: every destination type's K3 backward (independent chains); all outputs
-        # allocated here on the main stream
-        jobs = []
-        ai = 0
-        pre_jobs = []
-        # sampled blocks on one lane: a destination type that K2s will write (its relations'
-        # sources) gets its block gradient unzeroed, the first K2 round writing past the prefix
-        one_lane = (_Lanes(saved[0].device, 2).side is None
-                    and not any(any(g.pre) for g in spec.groups))
-        k2_targets = {src for g in spec.groups for src, csr in g.rels
-                      if need_x[src] and csr.num_edges > 0}
-        prefix: Dict[str, int] = {}
-        for gi, g in enumerate(spec.groups):
-            aggrs = aggrs_all[ai:ai + _n_main_rels(g)]
-            ai += _n_main_rels(g)
-            dout = douts[gi]
-            w, b = wbs[gi]
-            need_w, need_b = need[nt + 2 * gi], (b is not None and need[nt + 2 * gi + 1])
-            if dout is None:
+        # the types some K2 of this backward adds into: sources of the groups that got a
+        # gradient.  (autograd materialises the gradient of an unused output as zeros, so through
+        # ``hetero_layer`` every group has one today and a None ``dout`` is not reached)
+        k2_targets = {src for p, dout in zip(plan.groups, douts) if dout is not None
+                      for src, csr in p.rels if need_x[src] and csr.num_edges > 0}
+        prefix: Dict[str, int] = {}     # type -> rows of its unzeroed gradient written so far
+        # phase 1: every destination type's K3 backward; the groups with pre-projected
+        # relations after the others (their root gradient adds into what those wrote)
+        gis, jobs, pre_groups = [], [], []
+        for gi, p in enumerate(plan.groups):
+            if douts[gi] is None:
                 continue
-            if any(g.pre):
-                pre_jobs.append((gi, g, aggrs, w, dout.contiguous(), need_w, need_b,
-                                 ctx.masks[gi]))
+            if any(p.pre):
+                pre_groups.append(gi)
                 continue
-            dxs: List[Optional[torch.Tensor]] = []
-            for (src, csr), a in zip(g.rels, aggrs):
-                if need_x[src] and csr.num_edges > 0:
-                    dA = torch.empty_like(a)
-                    dxs.append(dA)
-                    pending.setdefault(src, []).append((dA, csr))
-                else:
-                    dxs.append(None)
-            segs = list(aggrs)
-            if g.root:
-                segs.append(_root(g, xs))
-                fresh = one_lane and _root_type(g) in k2_targets
-                dxs.append(_root_grad_buffer(g, xs, gx, prefix if fresh else None)
-                           if need_x[_root_type(g)] else None)
-            jobs.append((gi, g, segs, w, dout.contiguous(), dxs, need_w, need_b))
-        lanes = _Lanes(saved[0].device, len(jobs))
-        if one_lane and lanes.side is None:
+            dxs = _main_dxs(p, aggrs_by_g[gi], need_x, pending)
+            segs = list(aggrs_by_g[gi])
+            if p.root:
+                segs.append(_root(p, xs[p.root_type]))
+                dxs.append(None)
+                if need_x[p.root_type]:
+                    fresh = _fresh_prefix(plan, gi, need_x, k2_targets)
+                    if fresh is not None:
+                        prefix[p.root_type] = fresh
+                    dxs[-1] = _root_grad(p, xs, gx, fresh)
+            gis.append(gi)
+            jobs.append(BwdJob(segs, wbs[gi][0], douts[gi].contiguous(),
+                               outs[gi] if p.relu else None, dxs, need_w[gi], need_b[gi],
+                               ctx.masks[gi]))
+        if plan.batched:
             # one native call for the destination types' K3 backward (hgnn_linear_bwd_multi)
-            res = linear_bwd_many([(segs, w, dout, outs[gi] if g.relu else None, dxs, need_w,
-                                    need_b, ctx.masks[gi])
-                                   for gi, g, segs, w, dout, dxs, need_w, need_b in jobs])
-            for (gi, *_), (dw, db) in zip(jobs, res):
-                gwb[2 * gi], gwb[2 * gi + 1] = dw, db
-            jobs = []
-        for li, (gi, g, segs, w, dout, dxs, need_w, need_b) in enumerate(jobs):
-            with lanes.ctx(li):
-                dw, db = linear_bwd(segs, w, dout, outs[gi] if g.relu else None, dxs, need_w,
-                                    need_b, mask=ctx.masks[gi])
-            lanes.escape(li, dw, db)
+            res = linear_bwd_many(jobs)
+        else:
+            res = [_linear_bwd_of(j) for j in jobs]
+        for gi, (dw, db) in zip(gis, res):
             gwb[2 * gi], gwb[2 * gi + 1] = dw, db
-        lanes.join()
-        # groups with pre-projected relations (main stream): dz once, the destination update's
-        # backward on it, then per pre-projected relation the K2 of dz into the projected source
-        # rows and the projection's backward
-        for gi, g, aggrs, w, dout, need_w, need_b, mk in pre_jobs:
+        # groups with pre-projected relations: dz once, the destination update's backward on
+        # it, then per pre-projected relation the K2 of dz into the projected source rows and
+        # the projection's backward
+        for gi in pre_groups:
             gwb[2 * gi], gwb[2 * gi + 1] = _pre_group_backward(
-                g, xs, aggrs, w, dout, outs[gi], need_x, need_w, need_b, gx, pending, mk)
-        # phase 2: K2 per target type (different targets are independent chains)
+                plan.groups[gi], xs, aggrs_by_g[gi], wbs[gi][0], douts[gi].contiguous(), outs[gi],
+                need_x, need_w[gi], need_b[gi], gx, pending, ctx.masks[gi])
+        # phase 2: K2 per target type, as rounds of one launch each where they qualify
         for t in pending:
             if gx[t] is None:
                 gx[t] = torch.zeros_like(xs[t])
-        lanes = _Lanes(saved[0].device, len(pending))
-        if lanes.side is None and len(pending) > 1 and _k2_rounds(pending, gx, prefix):
-            return (None, *[gx[t] for t in spec.types], *gwb)
-        for t, n in prefix.items():          # (no rounds after all: zero what K2s add into)
-            gx[t][n:].zero_()
-        for li, (t, items) in enumerate(pending.items()):
-            with lanes.ctx(li):
+        if not (len(pending) > 1 and _k2_rounds(pending, gx, prefix)):
+            for t, n in prefix.items():      # (no rounds after all: zero what K2s add into)
+                gx[t][n:].zero_()
+            for t, items in pending.items():
                 for dA, csr in items:
                     scatter_mean_bwd(dA, csr, out=gx[t])
-        lanes.join()
-        return (None, *[gx[t] for t in spec.types], *gwb)
+        return (None, *[gx[t] for t in plan.types], *gwb)
+
+
+def _root_grad(p: _GroupPlan, xs, gx, fresh: Optional[int] = None) -> torch.Tensor:
+    """Allocates the gradient of the group's root input in ``gx`` and returns the rows the root
+    segment's dgrad writes.  A block's rows after its roots are zero until the K2s add into
+    them — or, with ``fresh`` (``_fresh_prefix``), left unwritten for the first K2 round."""
+    zero = p.prefix is not None and fresh is None
+    gx[p.root_type] = (torch.zeros_like if zero else torch.empty_like)(xs[p.root_type])
+    return _root(p, gx[p.root_type])
 
 
 def _k2_rounds(pending, gx, prefix=None) -> bool:
@@ -1339,28 +1364,6 @@ def _k2_rounds(pending, gx, prefix=None) -> bool:
     return True
 
 
-def _group_columns(g: DstGroup, xs) -> List[Tuple[int, int]]:
-    """(offset, width) of each relation's lin_l block in the group's fused weight."""
-    cols, o = [], 0
-    for src, _ in g.rels:
-        k = int(xs[src].shape[1])
-        cols.append((o, k))
-        o += k
-    return cols
-
-
-def _n_main_rels(g: DstGroup) -> int:
-    return sum(1 for i in range(len(g.rels)) if not (g.pre and g.pre[i]))
-
-
-def _main_weight(g: DstGroup, w: torch.Tensor, cols) -> torch.Tensor:
-    """The fused weight without the pre-projected relations' lin_l blocks."""
-    keep = [w[:, o:o + k] for (o, k), pre in zip(cols, g.pre) if not pre]
-    if g.root:
-        keep.append(w[:, cols[-1][0] + cols[-1][1]:] if cols else w)
-    return torch.cat(keep, dim=1).contiguous()
-
-
 def relu_grad(dout: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     """dz = dout * (out > 0): ReLU's backward from its output (one streaming pass)."""
     dz = torch.empty_like(dout)
@@ -1373,48 +1376,31 @@ def relu_grad(dout: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
     return dz
 
 
-def _pre_group_backward(g: DstGroup, xs, aggrs, w, dout, y, need_x, need_w, need_b, gx,
+def _pre_group_backward(g: _GroupPlan, xs, aggrs, w, dout, y, need_x, need_w, need_b, gx,
                         pending, mask=None):
     """Backward of a destination group with pre-projected relations: returns (dW, db) in the
     fused weight's column layout; source gradients go to ``gx`` / ``pending`` (K2 list)."""
-    cols = _group_columns(g, xs)
     # the destination update's backward over the remaining segments also writes the masked dz
     # that the pre-projected relations' K2 scatters (from the pass that masks it anyway)
     dz = torch.empty_like(dout) if g.relu else dout
-    segs, seg_cols, dxs = [], [], []
-    ai = 0
-    for (src, csr), pre, c in zip(g.rels, g.pre, cols):
-        if pre:
-            continue
-        a = aggrs[ai]
-        ai += 1
-        segs.append(a)
-        seg_cols.append(c)
-        if need_x[src] and csr.num_edges > 0:
-            dA = torch.empty_like(a)
-            dxs.append(dA)
-            pending.setdefault(src, []).append((dA, csr))
-        else:
-            dxs.append(None)
+    segs = list(aggrs)
+    seg_cols = [g.cols[i] for i in g.main]
+    dxs = _main_dxs(g, aggrs, need_x, pending)
     dx_add = [False] * len(dxs)
     if g.root:
-        segs.append(_root(g, xs))
-        o = cols[-1][0] + cols[-1][1] if cols else 0
-        seg_cols.append((o, int(w.shape[1]) - o))
-        if need_x[g.dst]:
-            # the root gradient is added into the destination table's gradient in the dgrad pass
-            # when another update already wrote it (no separate add); else it is that gradient
-            # (a block's prefix of a zeroed table: its other rows wait for the K2s)
-            dx_add.append(gx[g.dst] is not None)
-            if gx[g.dst] is None:
-                gx[g.dst] = (torch.empty_like(xs[g.dst]) if g.n_root is None
-                             else torch.zeros_like(xs[g.dst]))
-            dxs.append(gx[g.dst] if g.n_root is None else gx[g.dst][:g.n_root])
+        segs.append(_root(g, xs[g.root_type]))
+        seg_cols.append((g.root_col, int(w.shape[1]) - g.root_col))
+        # the root gradient is added into the destination table's gradient in the dgrad pass
+        # when another update already wrote it (no separate add); else it is that gradient
+        # (a block's prefix of a zeroed table: its other rows wait for the K2s)
+        held = need_x[g.root_type] and gx[g.root_type] is not None
+        dx_add.append(held)
+        if need_x[g.root_type]:
+            dxs.append(_root(g, gx[g.root_type]) if held else _root_grad(g, xs, gx))
         else:
             dxs.append(None)
-            dx_add.append(False)
     dw = torch.empty_like(w) if need_w else None
-    dw_main, db = linear_bwd(segs, _main_weight(g, w, cols), dout, y if g.relu else None, dxs,
+    dw_main, db = linear_bwd(segs, _main_weight(g, w), dout, y if g.relu else None, dxs,
                              need_w, need_b, dz_out=dz if g.relu else None, mask=mask,
                              dx_add=dx_add)
     if dw is not None:
@@ -1423,7 +1409,7 @@ def _pre_group_backward(g: DstGroup, xs, aggrs, w, dout, y, need_x, need_w, need
             dw[:, co:co + k].copy_(dw_main[:, o:o + k])
             o += k
     # pre-projected relations: dP = K2(dz) over the CSC, then P = x_src W_r^T's backward
-    for (src, csr), pre, (o, k) in zip(g.rels, g.pre, cols):
+    for (src, csr), pre, (o, k) in zip(g.rels, g.pre, g.cols):
         if not pre:
             continue
         x_src = xs[src]
@@ -1442,31 +1428,17 @@ def _pre_group_backward(g: DstGroup, xs, aggrs, w, dout, y, need_x, need_w, need
 def hetero_layer(spec: LayerSpec, x_dict: Dict[str, torch.Tensor],
                  weights: Sequence[Tuple[torch.Tensor, Optional[torch.Tensor]]]
                  ) -> Dict[str, torch.Tensor]:
-    for g in spec.groups:
-        if any(g.static) and (g.n_root is not None or g.root_src is not None):
-            # a block's tables are buffers native kernels refill through raw pointers (no
-            # version bump): an aggregate kept from them would be replayed stale
-            raise ValueError("hetero_layer: a sampled block's relations are never static")
+    plan = _layer_plan(spec, {t: tuple(x_dict[t].shape) for t in spec.types},
+                       [int(w.shape[0]) for w, _ in weights],
+                       resolve_row_dtype(spec.row_dtype) == "bf16")
     flat: List[Optional[torch.Tensor]] = [x_dict[t] for t in spec.types]
     for w, b in weights:
         flat.extend([w, b])
     N.require_device(*[t for t in flat if t is not None])
     for t in flat[:len(spec.types)]:
         _check_f32(t, "node features")
-    for g in spec.groups:
-        if g.root_src is not None:
-            if any(g.pre) or g.n_root is not None or not g.root:
-                raise ValueError("hetero_layer: root_src takes a root segment, no n_root and no "
-                                 "pre-projected relation")
-            n = int(x_dict[g.root_src].shape[0])
-        else:
-            n = int(x_dict[g.dst].shape[0]) if g.n_root is None else int(g.n_root)
-        for src, csr in g.rels:
-            if csr.n_dst != n or csr.n_src != int(x_dict[src].shape[0]):
-                raise ValueError(f"hetero_layer: relation {src}->{g.dst} is {csr.n_src}->"
-                                 f"{csr.n_dst} rows, the tables give {x_dict[src].shape[0]}->{n}")
-    outs = _HeteroLayer.apply(spec, *flat)
-    return {g.dst: y for g, y in zip(spec.groups, outs)}
+    outs = _HeteroLayer.apply(plan, *flat)
+    return {p.dst: y for p, y in zip(plan.groups, outs)}
 
 
 # ----------------------------------------------------------------------------- link loss
@@ -1660,40 +1632,35 @@ def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total:
     else:
         neg = neg_u_order.contiguous() if neg32 else neg_u_order.to(torch.int64).contiguous()
     dP = torch.empty(P.shape, dtype=torch.float32, device=dev)
-    # dP chain (side stream under HGNN_STREAMS=1): sort the negatives (post, user) by post,
-    # then the two dP gathers, each edge's weight recomputed from <U[u], P[post]>
-    # (hgnn_score_gather); pass A (loss + dU) needs none of it.
-    lanes = _Lanes(dev, 2)
-    with lanes.ctx(1):
-        if presorted is not None:
-            presorted.check_edges(csr, np_)
-            rowptr_n, nu_s = presorted.rowptr, presorted.users
-        else:
-            rowptr_n, nu_s = _sort_negatives(csr, neg_u_order, draw, neg, neg32, uop, E, np_,
-                                             err, dev)
+    # dP chain: sort the negatives (post, user) by post, then the two dP gathers, each edge's
+    # weight recomputed from <U[u], P[post]> (hgnn_score_gather); pass A (loss + dU) needs none
+    # of it.
+    if presorted is not None:
+        presorted.check_edges(csr, np_)
+        rowptr_n, nu_s = presorted.rowptr, presorted.users
+    else:
+        rowptr_n, nu_s = _sort_negatives(csr, neg_u_order, draw, neg, neg32, uop, E, np_, err,
+                                         dev)
     if ready is not None and p_chunks is None:
         # P is still arriving (parallel.py's all-gather of the post table): the sort above
         # needs only the edges, so it ran ahead; every kernel below reads P
         ready()
-        if lanes.side is not None:
-            lanes.side.wait_stream(lanes.main)
-    with lanes.ctx(1):
-        from .graph import NO_SPLIT, GroupedEdges, Plan
-        negs = GroupedEdges(rowptr_n, nu_s, nu_s, Plan(NO_SPLIT, 0, 0, None, None), np_)
-        if p_chunks is not None:
-            for lo, hi, rdy in p_chunks:
-                if rdy is not None:
-                    rdy()
-                if hi > lo:
-                    ng = GroupedEdges(rowptr_n[lo:hi + 1], nu_s, None,
-                                      Plan(NO_SPLIT, 0, 0, None, None), hi - lo)
-                    _score_gather2(U, P[lo:hi], _row_range(pf, lo, hi), ng, c, inv_e, dP[lo:hi])
-        else:
-            # (Measured and not kept, round 5: this gather in 8 source-block passes like K1,
-            # 32.83 vs 31.32 ms at cfg4 — each pass re-reads its rows' P vectors and dP.)
-            _score_gather2(U, P, pf, negs, c, inv_e, dP)
-        if on_dP is not None:
-            on_dP(dP)
+    from .graph import NO_SPLIT, GroupedEdges, Plan
+    negs = GroupedEdges(rowptr_n, nu_s, nu_s, Plan(NO_SPLIT, 0, 0, None, None), np_)
+    if p_chunks is not None:
+        for lo, hi, rdy in p_chunks:
+            if rdy is not None:
+                rdy()
+            if hi > lo:
+                ng = GroupedEdges(rowptr_n[lo:hi + 1], nu_s, None,
+                                  Plan(NO_SPLIT, 0, 0, None, None), hi - lo)
+                _score_gather2(U, P[lo:hi], _row_range(pf, lo, hi), ng, c, inv_e, dP[lo:hi])
+    else:
+        # (Measured and not kept, round 5: this gather in 8 source-block passes like K1,
+        # 32.83 vs 31.32 ms at cfg4 — each pass re-reads its rows' P vectors and dP.)
+        _score_gather2(U, P, pf, negs, c, inv_e, dP)
+    if on_dP is not None:
+        on_dP(dP)
     if ready is not None and p_chunks is not None:
         ready()                                 # all of P, for the scoring pass
     # (The scoring pass takes no col_hot: with the positives' cold rows read nt it measured
@@ -1724,7 +1691,6 @@ def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total:
                 N.ptr(neg), None, n_total, N.ptr(c), N.ptr(dU), None, None, None, None,
                 N.ptr(part), N.ptr(loss), N.ptr(err if check else None), s),
                 "hgnn_edge_score_fwd")
-    lanes.join()
     if check and int(err[0]):
         raise ValueError("edge_bce_loss: negative post id out of range")
     return loss, dU, dP
