@@ -704,6 +704,31 @@ size_t hgnn_score_topk_bf16_lds_bytes(int32_t d, int32_t L);
 int hgnn_score_topk_bf16(const uint16_t* U, const int32_t* rows, int64_t n_rows,
                          const uint16_t* P, int64_t n_cand, int32_t d, int32_t L, float* topv,
                          int32_t* topi, hgnn_stream_t stream);
+/* hgnn_score_topk / hgnn_score_topk_bf16 with per-row exclusion lists (serving: leave out the
+ * posts a user has already engaged with): output row r never lists the candidates
+ * excl_col[excl_rowptr[e] .. excl_rowptr[e + 1]), e = excl_rows ? excl_rows[r] : r.  excl_rows is
+ * independent of rows: with both set to the same user ids, U and the lists are keyed alike.
+ * Caller's contract, not checked (it would take a pass and a sync): each list strictly ascending,
+ * its entries in [0, n_cand), excl_rowptr non-decreasing.  The kernel tests the exclusion where it
+ * masks the candidates past n_cand, before the threshold test, so an excluded candidate never
+ * reaches a list; each list is walked once, at most one chunk's entries per chunk.
+ * A row with fewer than L candidates left ends with empty slots: topv = -inf, topi = -1.  Such
+ * lists are not input for hgnn_topk_finish, which expects L real entries per row.
+ * Everything else is hgnn_score_topk's contract: d in {64, 128}; U and P row-major, 16-B aligned;
+ * 1 <= L <= min(64, n_cand); score desc then index asc; no sync, no allocation,
+ * graph-capturable; the same argument checks and error codes, and HGNN_E_ARG for a null
+ * excl_rowptr or excl_col.  The dynamic LDS is that of the plain kernels (the bf16 launch may
+ * choose the other chunk size than hgnn_score_topk_bf16_lds_bytes reports: the excluding kernel
+ * holds more registers, which changes where a 32-candidate chunk buys a resident workgroup). */
+int hgnn_score_topk_excl(const float* U, const int32_t* rows, int64_t n_rows, const float* P,
+                         int64_t n_cand, int32_t d, int32_t L, const int32_t* excl_rowptr,
+                         const int32_t* excl_col, const int32_t* excl_rows, float* topv,
+                         int32_t* topi, hgnn_stream_t stream);
+int hgnn_score_topk_excl_bf16(const uint16_t* U, const int32_t* rows, int64_t n_rows,
+                              const uint16_t* P, int64_t n_cand, int32_t d, int32_t L,
+                              const int32_t* excl_rowptr, const int32_t* excl_col,
+                              const int32_t* excl_rows, float* topv, int32_t* topi,
+                              hgnn_stream_t stream);
 /* Recall / NDCG (as hgnn_topk_metrics) from hgnn_score_topk or hgnn_score_topk_bf16 lists with
  * L = min(K, n_cand) + 1 (or min(K, n_cand) when n_cand <= K).  A row whose K-th value ties the
  * (K+1)-th needs the whole row for sklearn's tie groups: it gets tie_flag = 1 and no outputs;

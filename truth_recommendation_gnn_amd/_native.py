@@ -131,6 +131,10 @@ _SIGS = {
     "hgnn_score_topk": (_c_i32, [_p, _p, _c_i64, _p, _c_i64, _c_i32, _c_i32, _p, _p, _p]),
     "hgnn_score_topk_bf16_lds_bytes": (_c_sz, [_c_i32, _c_i32]),
     "hgnn_score_topk_bf16": (_c_i32, [_p, _p, _c_i64, _p, _c_i64, _c_i32, _c_i32, _p, _p, _p]),
+    "hgnn_score_topk_excl": (_c_i32, [_p, _p, _c_i64, _p, _c_i64, _c_i32, _c_i32, _p, _p, _p, _p,
+                                      _p, _p]),
+    "hgnn_score_topk_excl_bf16": (_c_i32, [_p, _p, _c_i64, _p, _c_i64, _c_i32, _c_i32, _p, _p,
+                                           _p, _p, _p, _p]),
     "hgnn_topk_finish": (_c_i32, [_p, _p, _c_i64, _c_i32, _c_i64, _c_i32, _p, _p, _p, _p, _p, _p,
                                   _p]),
     "hgnn_edge_score_parts": (_c_i64, [_c_i64]),

@@ -270,6 +270,68 @@ constexpr int kStUsersPerWave = 32;
 constexpr int kStWaves = 4;
 constexpr int kStThreads = kStWaves * 64;
 
+// Per-row exclusion lists (the EXCL instantiations of the two kernels below): output row r never
+// lists the candidates col[rowptr[e] .. rowptr[e + 1]), e = rows ? rows[r] : r, each list strictly
+// ascending.  One lane per user of the wave's tile owns that user's list: a cursor, the two entries
+// under it (held in registers: a chunk without excluded candidates costs no load, and the entry a
+// step tests was loaded a step earlier, so the walk waits for memory only where one user excludes
+// several candidates of one chunk) and, per chunk, a bit mask of the chunk's excluded candidates.
+// The lists are walked once per kernel; nothing is ever addressed with a value read from col.
+struct StExcl {
+  const int32_t* rowptr;
+  const int32_t* col;
+  const int32_t* rows;
+};
+
+struct StExclCursor {
+  int cur = 0, end = 0;     // col[cur .. end) is still ahead of the candidate stream
+  int next = INT_MAX;       // col[cur], INT_MAX once the list is used up
+  int next2 = INT_MAX;      // col[cur + 1], likewise
+  uint32_t lo = 0, hi = 0;  // this chunk's excluded candidates: bit b = candidate chunk * TC + b
+
+  __device__ __forceinline__ int at(const StExcl& x, int k) const {
+    return k < end ? x.col[k] : INT_MAX;
+  }
+  __device__ __forceinline__ void open(const StExcl& x, bool owner, int64_t r) {
+    if (!owner) return;     // rows past n_rows and lanes without a user: an empty list
+    const int64_t e = x.rows ? (int64_t)x.rows[r] : r;
+    cur = x.rowptr[e];
+    end = x.rowptr[e + 1];
+    next = at(x, cur);
+    next2 = at(x, cur + 1);
+  }
+  // Collect the entries below the end of chunk ch (at most TC steps; entries are < C, so INT_MAX
+  // never is).  Returns, wave-uniformly, whether any lane of the wave has a bit set.  Call it in
+  // front of the prefetch of the next chunk's rows: loads return in order, so what a step waits
+  // for is then an entry requested chunks ago, not the rows just requested.
+  template <int TC>
+  __device__ __forceinline__ bool advance(const StExcl& x, int64_t ch, int64_t C) {
+    const int cend = (int)((ch + 1) * TC < C ? (ch + 1) * TC : C);
+    lo = hi = 0;
+    while (next < cend) {
+      const int b = next & (TC - 1);   // chunks start at multiples of TC
+      if (TC == 64 && b >= 32) hi |= 1u << (b - 32);
+      else lo |= 1u << b;
+      ++cur;
+      next = next2;
+      next2 = at(x, cur + 1);
+    }
+    return __ballot((lo | hi) != 0u) != 0ull;
+  }
+  // The chunk's mask of a user, from the lane that owns the user: fetched once per chunk, in
+  // front of the MFMA work, which hides the shuffle's latency.
+  template <int TC>
+  __device__ __forceinline__ void fetch(int owner, uint32_t& mlo, uint32_t& mhi) const {
+    mlo = __shfl(lo, owner, 64);
+    mhi = TC == 64 ? __shfl(hi, owner, 64) : 0u;
+  }
+  // Its 4 bits of candidates 16 tile + 4 g .. + 3 of the chunk.
+  static __device__ __forceinline__ uint32_t tile_bits(uint32_t mlo, uint32_t mhi, int tile,
+                                                       int g) {
+    return ((tile < 2 ? mlo : mhi) >> ((tile & 1) * 16 + 4 * g)) & 0xFu;
+  }
+};
+
 struct ScoreTopkArgs {
   const float* U;         // [n_u_rows][d] user embeddings
   const int32_t* rows;    // null, or the U row of each output row
@@ -279,6 +341,7 @@ struct ScoreTopkArgs {
   int32_t L;              // list length, 1..64
   float* topv;            // [n_rows][L] scores, best first
   int32_t* topi;          // [n_rows][L] candidate indices
+  StExcl x;               // read by the excluding instantiations only
 };
 
 template <int D>
@@ -304,7 +367,9 @@ __device__ __forceinline__ void st_insert(float* lvs, int* lis, int L, int lane,
   newthr = (pos == L - 1) ? cs : __shfl(v, L - 2 < 0 ? 0 : L - 2, 64);
 }
 
-template <int D>
+// The write-out of the lists: with exclusions a row can end with fewer than L entries, and its
+// empty slots (the in-LDS sentinel) leave as score -inf, index -1.
+template <int D, bool EXCL>
 __global__ void __launch_bounds__(kStThreads) k_score_topk(const ScoreTopkArgs a) {
   using Cfg = StCfg<D>;
   constexpr int TC = Cfg::TC, S = Cfg::S, KC = Cfg::KC, LOADS = Cfg::LOADS;
@@ -336,6 +401,8 @@ __global__ void __launch_bounds__(kStThreads) k_score_topk(const ScoreTopkArgs a
   }
   const int64_t C = a.n_cand;
   const int64_t n_chunks = (C + TC - 1) / TC;
+  StExclCursor xc;   // lane u < 32 owns user u of the wave
+  if constexpr (EXCL) xc.open(a.x, lane < kStUsersPerWave && row0 + lane < a.n_rows, row0 + lane);
   // chunk staging: thread t loads float4 number t + kStThreads q of the chunk (row-major TC x D)
   float4 nxt[LOADS];
   auto load_chunk = [&](int64_t ch) {
@@ -361,7 +428,16 @@ __global__ void __launch_bounds__(kStThreads) k_score_topk(const ScoreTopkArgs a
   __syncthreads();
   for (int64_t ch = 0; ch < n_chunks; ++ch) {
     const int buf = (int)(ch & 1);
+    bool anyx = false;   // wave-uniform: some user of the wave excludes a candidate of this chunk
+    if constexpr (EXCL) anyx = xc.template advance<TC>(a.x, ch, C);
     if (ch + 1 < n_chunks) load_chunk(ch + 1);   // in flight during the MFMA work below
+    uint32_t xlo[2] = {0u, 0u}, xhi[2] = {0u, 0u};   // the masks of this lane's two users
+    if constexpr (EXCL) {
+      if (anyx) {
+        xc.template fetch<TC>(i, xlo[0], xhi[0]);
+        xc.template fetch<TC>(16 + i, xlo[1], xhi[1]);
+      }
+    }
     const float* cb = cbuf + buf * TC * S;
 #pragma unroll
     for (int t = 0; t < TC / 16; t += 2) {
@@ -395,6 +471,17 @@ __global__ void __launch_bounds__(kStThreads) k_score_topk(const ScoreTopkArgs a
 #pragma unroll
           for (int j = 0; j < 4; ++j)
             if (cbase + j >= C) acc[tt][nt][j] = -__builtin_inff();   // never >= any thr
+        if constexpr (EXCL) {
+          if (anyx) {
+#pragma unroll
+            for (int nt = 0; nt < 2; ++nt) {
+              const uint32_t xb = StExclCursor::tile_bits(xlo[nt], xhi[nt], t + tt, g);
+#pragma unroll
+              for (int j = 0; j < 4; ++j)
+                if (xb >> j & 1u) acc[tt][nt][j] = -__builtin_inff();
+            }
+          }
+        }
         bool any = false;
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
@@ -433,8 +520,11 @@ __global__ void __launch_bounds__(kStThreads) k_score_topk(const ScoreTopkArgs a
     const int64_t r = row0 + u;
     if (r >= a.n_rows) break;
     if (lane < L) {
-      a.topv[r * L + lane] = lvw[u * L + lane];
-      a.topi[r * L + lane] = liw[u * L + lane];
+      float v = lvw[u * L + lane];
+      int x = liw[u * L + lane];
+      if (EXCL && x == INT_MAX) { v = -__builtin_inff(); x = -1; }   // an empty slot
+      a.topv[r * L + lane] = v;
+      a.topi[r * L + lane] = x;
     }
   }
 }
@@ -467,6 +557,7 @@ struct ScoreTopkBf16Args {
   int32_t L;              // list length, 1..64
   float* topv;            // [n_rows][L] scores, best first
   int32_t* topi;          // [n_rows][L] candidate indices
+  StExcl x;               // read by the excluding instantiations only
 };
 
 constexpr int kSt16Waves = 8;
@@ -485,19 +576,21 @@ constexpr size_t st16_lds_bytes(int d, int L, int tc) {
 
 // Workgroups of this (d, L, chunk) that fit a CU: by LDS, and by wave slots (4 x 8 waves fill the
 // CU's 32; the d = 128, 64-candidate kernel holds 68 VGPRs, 7 waves per SIMD: 3 workgroups).
-inline int st16_resident(int d, int L, int tc) {
+// The excluding kernels hold the cursor and the chunk's mask on top: 63 VGPRs at (64, 32), 71 at
+// (64, 64), 72 at (128, 32), 80 at (128, 64), so only the first keeps 8 waves per SIMD.
+inline int st16_resident(int d, int L, int tc, bool excl) {
   const int by_lds = (int)(kSt16LdsLimit / st16_lds_bytes(d, L, tc));
-  const int cap = (d == 128 && tc == 64) ? 3 : 4;
+  const int cap = excl ? ((d == 64 && tc == 32) ? 4 : 3) : ((d == 128 && tc == 64) ? 3 : 4);
   return by_lds < cap ? by_lds : cap;
 }
 
 // Candidates per chunk: 64 (half the barriers), or 32 where that makes room for a workgroup more.
-inline int st16_chunk(int d, int L) {
+inline int st16_chunk(int d, int L, bool excl) {
   if (HGNN_ST16_TC == 32 || HGNN_ST16_TC == 64) return HGNN_ST16_TC;
-  return st16_resident(d, L, 32) > st16_resident(d, L, 64) ? 32 : 64;
+  return st16_resident(d, L, 32, excl) > st16_resident(d, L, 64, excl) ? 32 : 64;
 }
 
-template <int D, int TC>
+template <int D, int TC, bool EXCL>
 __global__ void __launch_bounds__(kSt16Threads) k_score_topk_bf16(const ScoreTopkBf16Args a) {
   constexpr int S = D + 16;                     // LDS row stride, halfwords
   constexpr int KS = D / 32;                    // k-steps (MFMAs) per tile
@@ -530,6 +623,8 @@ __global__ void __launch_bounds__(kSt16Threads) k_score_topk_bf16(const ScoreTop
   }
   const int64_t C = a.n_cand;
   const int64_t n_chunks = (C + TC - 1) / TC;
+  StExclCursor xc;   // lane u < 16 owns user u of the wave
+  if constexpr (EXCL) xc.open(a.x, lane < 16 && row0 + lane < a.n_rows, row0 + lane);
   // chunk staging: thread t loads 16-B piece t + 512 q of the chunk (row-major TC x D)
   uint4 nxt[LOADS];
   auto load_chunk = [&](int64_t ch) {
@@ -555,7 +650,13 @@ __global__ void __launch_bounds__(kSt16Threads) k_score_topk_bf16(const ScoreTop
   __syncthreads();
   for (int64_t ch = 0; ch < n_chunks; ++ch) {
     const int buf = (int)(ch & 1);
+    bool anyx = false;   // wave-uniform: some user of the wave excludes a candidate of this chunk
+    if constexpr (EXCL) anyx = xc.template advance<TC>(a.x, ch, C);
     if (ch + 1 < n_chunks) load_chunk(ch + 1);   // in flight during the work below
+    uint32_t xlo = 0u, xhi = 0u;   // the mask of this lane's user
+    if constexpr (EXCL) {
+      if (anyx) xc.template fetch<TC>(i, xlo, xhi);
+    }
     const uint16_t* cb = cbuf + buf * TC * S;
     const bool ragged = (ch + 1) * TC > C;       // only the last chunk can hold rows past C
 #pragma unroll
@@ -582,6 +683,14 @@ __global__ void __launch_bounds__(kSt16Threads) k_score_topk_bf16(const ScoreTop
 #pragma unroll
           for (int j = 0; j < 4; ++j)
             if (cbase + j >= C) acc[tt][j] = -__builtin_inff();   // never >= any thr
+        }
+        if constexpr (EXCL) {
+          if (anyx) {
+            const uint32_t xb = StExclCursor::tile_bits(xlo, xhi, t + tt, g);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+              if (xb >> j & 1u) acc[tt][j] = -__builtin_inff();
+          }
         }
         const f32x4 v = acc[tt];
         const bool any = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])) >= thr;
@@ -615,18 +724,73 @@ __global__ void __launch_bounds__(kSt16Threads) k_score_topk_bf16(const ScoreTop
     const int64_t r = row0 + u;
     if (r >= a.n_rows) break;
     if (lane < L) {
-      a.topv[r * L + lane] = lvw[u * L + lane];
-      a.topi[r * L + lane] = liw[u * L + lane];
+      float v = lvw[u * L + lane];
+      int x = liw[u * L + lane];
+      if (EXCL && x == INT_MAX) { v = -__builtin_inff(); x = -1; }   // an empty slot
+      a.topv[r * L + lane] = v;
+      a.topi[r * L + lane] = x;
     }
   }
 }
 
-template <int D>
+template <int D, bool EXCL>
 static void launch_score_topk_bf16(int tc, unsigned blocks, size_t lds, hipStream_t stream,
                                    const ScoreTopkBf16Args& a) {
   const dim3 grid(blocks), block(kSt16Threads);
-  if (tc == 32) hipLaunchKernelGGL((k_score_topk_bf16<D, 32>), grid, block, lds, stream, a);
-  else hipLaunchKernelGGL((k_score_topk_bf16<D, 64>), grid, block, lds, stream, a);
+  if (tc == 32) hipLaunchKernelGGL((k_score_topk_bf16<D, 32, EXCL>), grid, block, lds, stream, a);
+  else hipLaunchKernelGGL((k_score_topk_bf16<D, 64, EXCL>), grid, block, lds, stream, a);
+}
+
+// The checks hgnn_score_topk, hgnn_score_topk_bf16 and their excluding forms share; *empty is set
+// when there is nothing to launch.
+static int score_topk_check(const char* what, const void* U, int64_t n_rows, const void* P,
+                            int64_t n_cand, int32_t d, int32_t L, const float* topv,
+                            const int32_t* topi, const StExcl* x, bool* empty) {
+  *empty = false;
+  if (n_rows < 0 || n_cand < 1 || n_cand >= INT_MAX || L < 1 || L > 64 || L > n_cand)
+    return fail(HGNN_E_ARG, "%s: rows=%lld cand=%lld L=%d", what, (long long)n_rows,
+                (long long)n_cand, L);
+  if (d != 64 && d != 128) return fail(HGNN_E_UNSUPPORTED, "%s: d=%d (64 or 128)", what, d);
+  if (x && (!x->rowptr || !x->col))
+    return fail(HGNN_E_ARG, "%s: null excl_rowptr or excl_col", what);
+  if (n_rows == 0) { *empty = true; return HGNN_OK; }
+  if (!U || !P || !topv || !topi) return fail(HGNN_E_ARG, "%s: null pointer", what);
+  if (reinterpret_cast<uintptr_t>(U) % 16 || reinterpret_cast<uintptr_t>(P) % 16)
+    return fail(HGNN_E_ARG, "%s: U and P must be 16-B aligned", what);
+  return HGNN_OK;
+}
+
+template <bool EXCL>
+static int score_topk_f32(const char* what, const float* U, const int32_t* rows, int64_t n_rows,
+                          const float* P, int64_t n_cand, int32_t d, int32_t L, const StExcl& x,
+                          float* topv, int32_t* topi, hipStream_t stream) {
+  bool empty;
+  const int rc = score_topk_check(what, U, n_rows, P, n_cand, d, L, topv, topi,
+                                  EXCL ? &x : nullptr, &empty);
+  if (rc != HGNN_OK || empty) return rc;
+  ScoreTopkArgs a{U, rows, n_rows, P, n_cand, L, topv, topi, x};
+  const size_t lds = hgnn_score_topk_lds_bytes(d, L);
+  const dim3 grid((unsigned)cdiv(n_rows, kStWaves * kStUsersPerWave)), block(kStThreads);
+  if (d == 64) hipLaunchKernelGGL((k_score_topk<64, EXCL>), grid, block, lds, stream, a);
+  else hipLaunchKernelGGL((k_score_topk<128, EXCL>), grid, block, lds, stream, a);
+  return check_launch("k_score_topk");
+}
+
+template <bool EXCL>
+static int score_topk_b16(const char* what, const uint16_t* U, const int32_t* rows,
+                          int64_t n_rows, const uint16_t* P, int64_t n_cand, int32_t d, int32_t L,
+                          const StExcl& x, float* topv, int32_t* topi, hipStream_t stream) {
+  bool empty;
+  const int rc = score_topk_check(what, U, n_rows, P, n_cand, d, L, topv, topi,
+                                  EXCL ? &x : nullptr, &empty);
+  if (rc != HGNN_OK || empty) return rc;
+  ScoreTopkBf16Args a{U, rows, n_rows, P, n_cand, L, topv, topi, x};
+  const int tc = st16_chunk(d, L, EXCL);
+  const size_t lds = st16_lds_bytes(d, L, tc);
+  const unsigned blocks = (unsigned)cdiv(n_rows, kSt16Users);
+  if (d == 64) launch_score_topk_bf16<64, EXCL>(tc, blocks, lds, stream, a);
+  else launch_score_topk_bf16<128, EXCL>(tc, blocks, lds, stream, a);
+  return check_launch("k_score_topk_bf16");
 }
 
 // Metrics from the fused lists: one wave per row; rows where a tie crosses the cut get
@@ -693,49 +857,39 @@ size_t hgnn_score_topk_lds_bytes(int32_t d, int32_t L) {
 
 int hgnn_score_topk(const float* U, const int32_t* rows, int64_t n_rows, const float* P,
                     int64_t n_cand, int32_t d, int32_t L, float* topv, int32_t* topi,
-                    hgnn_stream_t stream_) {
-  hipStream_t stream = as_stream(stream_);
-  if (n_rows < 0 || n_cand < 1 || n_cand >= INT_MAX || L < 1 || L > 64 || L > n_cand)
-    return fail(HGNN_E_ARG, "score_topk: rows=%lld cand=%lld L=%d", (long long)n_rows,
-                (long long)n_cand, L);
-  if (d != 64 && d != 128)
-    return fail(HGNN_E_UNSUPPORTED, "score_topk: d=%d (64 or 128)", d);
-  if (n_rows == 0) return HGNN_OK;
-  if (!U || !P || !topv || !topi) return fail(HGNN_E_ARG, "score_topk: null pointer");
-  if (reinterpret_cast<uintptr_t>(U) % 16 || reinterpret_cast<uintptr_t>(P) % 16)
-    return fail(HGNN_E_ARG, "score_topk: U and P must be 16-B aligned");
-  ScoreTopkArgs a{U, rows, n_rows, P, n_cand, L, topv, topi};
-  const size_t lds = hgnn_score_topk_lds_bytes(d, L);
-  const dim3 grid((unsigned)cdiv(n_rows, kStWaves * kStUsersPerWave)), block(kStThreads);
-  if (d == 64) hipLaunchKernelGGL(k_score_topk<64>, grid, block, lds, stream, a);
-  else hipLaunchKernelGGL(k_score_topk<128>, grid, block, lds, stream, a);
-  return check_launch("k_score_topk");
+                    hgnn_stream_t stream) {
+  return score_topk_f32<false>("score_topk", U, rows, n_rows, P, n_cand, d, L, StExcl{}, topv,
+                               topi, as_stream(stream));
+}
+
+int hgnn_score_topk_excl(const float* U, const int32_t* rows, int64_t n_rows, const float* P,
+                         int64_t n_cand, int32_t d, int32_t L, const int32_t* excl_rowptr,
+                         const int32_t* excl_col, const int32_t* excl_rows, float* topv,
+                         int32_t* topi, hgnn_stream_t stream) {
+  return score_topk_f32<true>("score_topk_excl", U, rows, n_rows, P, n_cand, d, L,
+                              StExcl{excl_rowptr, excl_col, excl_rows}, topv, topi,
+                              as_stream(stream));
 }
 
 size_t hgnn_score_topk_bf16_lds_bytes(int32_t d, int32_t L) {
-  return st16_lds_bytes(d, L, st16_chunk(d, L));
+  return st16_lds_bytes(d, L, st16_chunk(d, L, false));
 }
 
 int hgnn_score_topk_bf16(const uint16_t* U, const int32_t* rows, int64_t n_rows,
                          const uint16_t* P, int64_t n_cand, int32_t d, int32_t L, float* topv,
-                         int32_t* topi, hgnn_stream_t stream_) {
-  hipStream_t stream = as_stream(stream_);
-  if (n_rows < 0 || n_cand < 1 || n_cand >= INT_MAX || L < 1 || L > 64 || L > n_cand)
-    return fail(HGNN_E_ARG, "score_topk_bf16: rows=%lld cand=%lld L=%d", (long long)n_rows,
-                (long long)n_cand, L);
-  if (d != 64 && d != 128)
-    return fail(HGNN_E_UNSUPPORTED, "score_topk_bf16: d=%d (64 or 128)", d);
-  if (n_rows == 0) return HGNN_OK;
-  if (!U || !P || !topv || !topi) return fail(HGNN_E_ARG, "score_topk_bf16: null pointer");
-  if (reinterpret_cast<uintptr_t>(U) % 16 || reinterpret_cast<uintptr_t>(P) % 16)
-    return fail(HGNN_E_ARG, "score_topk_bf16: U and P must be 16-B aligned");
-  ScoreTopkBf16Args a{U, rows, n_rows, P, n_cand, L, topv, topi};
-  const int tc = st16_chunk(d, L);
-  const size_t lds = st16_lds_bytes(d, L, tc);
-  const unsigned blocks = (unsigned)cdiv(n_rows, kSt16Users);
-  if (d == 64) launch_score_topk_bf16<64>(tc, blocks, lds, stream, a);
-  else launch_score_topk_bf16<128>(tc, blocks, lds, stream, a);
-  return check_launch("k_score_topk_bf16");
+                         int32_t* topi, hgnn_stream_t stream) {
+  return score_topk_b16<false>("score_topk_bf16", U, rows, n_rows, P, n_cand, d, L, StExcl{},
+                               topv, topi, as_stream(stream));
+}
+
+int hgnn_score_topk_excl_bf16(const uint16_t* U, const int32_t* rows, int64_t n_rows,
+                              const uint16_t* P, int64_t n_cand, int32_t d, int32_t L,
+                              const int32_t* excl_rowptr, const int32_t* excl_col,
+                              const int32_t* excl_rows, float* topv, int32_t* topi,
+                              hgnn_stream_t stream) {
+  return score_topk_b16<true>("score_topk_excl_bf16", U, rows, n_rows, P, n_cand, d, L,
+                              StExcl{excl_rowptr, excl_col, excl_rows}, topv, topi,
+                              as_stream(stream));
 }
 
 int hgnn_topk_finish(const float* topv, const int32_t* topi, int64_t n_rows, int32_t L,

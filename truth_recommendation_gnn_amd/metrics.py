@@ -181,9 +181,146 @@ def topk_metrics(scores: torch.Tensor, true_rowptr: torch.Tensor, true_cand: tor
     return topk, recall, ndcg
 
 
+class SeenIndex:
+    """The posts each user has already engaged with, as ``recommend(..., exclude=)`` reads them:
+    ``rowptr`` (int32 ``[num_users + 1]``) and ``col`` (int32, ascending and unique per user) on
+    the device of ``edges``.  ``edges``: int ``[2, M]`` (user row, post index) pairs in any order,
+    duplicates allowed: the training graph's ('user', 'engages', 'post') edge_index as it is.
+    Build it once and reuse it for every call; the grouping is a device sort."""
+
+    def __init__(self, edges: torch.Tensor, num_users: int, num_posts: int):
+        dev = N.require_device(edges)
+        if edges.dim() != 2 or edges.shape[0] != 2 or edges.is_floating_point() or \
+                edges.is_complex() or edges.dtype == torch.bool:
+            raise ValueError("SeenIndex: edges must be an integer [2, M] tensor")
+        self.num_users, self.num_posts = int(num_users), int(num_posts)
+        if self.num_users < 0 or self.num_posts < 0 or self.num_posts >= 2 ** 31 or \
+                self.num_users >= 2 ** 31:
+            raise ValueError("SeenIndex: num_users and num_posts must lie in [0, 2^31)")
+        M = int(edges.shape[1])
+        if M >= 2 ** 31:
+            raise ValueError(f"SeenIndex: {M} edges; int32 row pointers hold fewer than 2^31")
+        e = edges.to(torch.int64)
+        u, p = e[0], e[1]
+        if M:
+            lo_u, hi_u, lo_p, hi_p = torch.stack([u.min(), u.max(), p.min(), p.max()]).tolist()
+            if lo_u < 0 or hi_u >= self.num_users:
+                raise ValueError(f"SeenIndex: user row outside [0, {self.num_users})")
+            if lo_p < 0 or hi_p >= self.num_posts:
+                raise ValueError(f"SeenIndex: post index outside [0, {self.num_posts})")
+        key = torch.unique(u * max(self.num_posts, 1) + p, sorted=True)   # deduped, (user, post)
+        per_user = torch.searchsorted(
+            key, torch.arange(1, self.num_users + 1, device=dev) * max(self.num_posts, 1))
+        self.rowptr = torch.cat([per_user.new_zeros(1), per_user]).to(torch.int32)
+        # one spare element: an index without edges still has a col pointer to hand to the library
+        self._col = torch.zeros(int(key.numel()) + 1, dtype=torch.int32, device=dev)
+        self._col[:-1] = key % max(self.num_posts, 1)
+        self.col = self._col[:-1]
+
+
+def _check_users(users: torch.Tensor, n_u: int) -> torch.Tensor:
+    if users.dim() != 1 or users.is_floating_point() or users.is_complex() or \
+            users.dtype == torch.bool:
+        raise ValueError("recommend: users must be a 1-D integer tensor of user_emb rows")
+    if users.numel():
+        lo, hi = torch.stack([users.min(), users.max()]).tolist()
+        if lo < 0 or hi >= n_u:
+            raise ValueError(f"recommend: users outside [0, {n_u})")
+    return users.to(torch.int32).contiguous()
+
+
+def _mask_seen(S: torch.Tensor, seen: SeenIndex, ids: torch.Tensor) -> None:
+    """S[r, c] = -inf for every post c that user ids[r] (int64) has seen."""
+    start = seen.rowptr[ids].long()
+    count = seen.rowptr[ids + 1].long() - start
+    total = int(count.sum())
+    if total == 0:
+        return
+    r = torch.repeat_interleave(torch.arange(ids.numel(), device=S.device), count,
+                                output_size=total)
+    first = torch.cumsum(count, 0) - count                 # of each row, in the flattened lists
+    c = seen.col[start[r] + (torch.arange(total, device=S.device) - first[r])].long()
+    S[r, c] = -math.inf
+
+
+def _recommend_subset(user_emb, post_emb, K, batch_scores, fused, row_dtype, users, exclude):
+    """``recommend`` with ``users`` and / or ``exclude``."""
+    bf16 = _bf16_rows(user_emb, post_emb, row_dtype, "recommend")
+    seen = exclude if isinstance(exclude, SeenIndex) or exclude is None else None
+    dev = N.require_device(user_emb, post_emb, users, seen.rowptr if seen is not None else exclude)
+    n_u, C = int(user_emb.shape[0]), int(post_emb.shape[0])
+    if C == 0:
+        raise ValueError("recommend: no posts to rank")
+    if exclude is not None and seen is None:
+        seen = SeenIndex(exclude, n_u, C)
+    if seen is not None and (seen.num_users, seen.num_posts) != (n_u, C):
+        raise ValueError(f"recommend: exclude was built for {seen.num_users} users x "
+                         f"{seen.num_posts} posts, the tables hold {n_u} x {C}")
+    users32 = None if users is None else _check_users(users, n_u)
+    n = n_u if users is None else int(users32.numel())
+    k = min(K, C)
+    d = int(user_emb.shape[1])
+    out_s = torch.empty(n, k, dtype=torch.float32, device=dev)
+    out_i = torch.empty(n, k, dtype=torch.int32, device=dev)
+    if n == 0:
+        return out_s, out_i.long()
+    lib = N.lib()
+    cast = bf16 and user_emb.dtype != torch.bfloat16       # row_dtype="bf16" on fp32 tables
+    if cast:
+        # only the selected rows are cast: row r of U is users[r]'s
+        U = ops.rows_to_bf16(user_emb if users is None else user_emb.index_select(0, users32))
+        rows = None
+    else:
+        U, rows = user_emb.contiguous(), users32
+    P = _as_bf16(post_emb) if bf16 else post_emb.contiguous()
+    if _fused_ok(d, fused) and k <= 64:
+        entry = "hgnn_score_topk" + ("_excl" if seen is not None else "") + \
+            ("_bf16" if bf16 else "")
+        excl = () if seen is None else (N.ptr(seen.rowptr), N.ptr(seen._col), N.ptr(users32))
+        N.check(getattr(lib, entry)(N.ptr(U), N.ptr(rows), n, N.ptr(P), C, d, k, *excl,
+                                    N.ptr(out_s), N.ptr(out_i), N.stream_ptr(dev)), entry)
+        return out_s, out_i.long()
+    # materialised: the scores of a block of rows, -inf at the excluded posts, then the K best in
+    # rounds of up to 63 (hgnn_topk_metrics' list) with each round's winners set to -inf.  That
+    # kernel never lists a -inf score, and what it leaves in the slots past a row's last real
+    # entry is not an index to read with (INT_MAX, or a padding position of its scan): the slots
+    # that hold an entry are counted from the scores instead.
+    ld = (C + 4) // 4 * 4                                  # 16-B rows and a padding column
+    P_c = torch.zeros(ld, d, dtype=torch.float32, device=dev)
+    P_c[:C] = P.float()
+    nb = max(1, min(n, batch_scores // ld))
+    buf = torch.empty(nb, ld, dtype=torch.float32, device=dev)
+    no_rel = torch.zeros(nb + 1, dtype=torch.int32, device=dev)   # empty relevance sets
+    scratch = torch.empty(2, nb, dtype=torch.float64, device=dev)
+    for r0 in range(0, n, nb):
+        r1 = min(n, r0 + nb)
+        S = buf[: r1 - r0]
+        U_r = U[r0:r1] if rows is None else U.index_select(0, rows[r0:r1])
+        torch.mm(U_r.float(), P_c.T, out=S)
+        if seen is not None:
+            _mask_seen(S, seen, (torch.arange(r0, r1, device=dev) if users32 is None
+                                 else users32[r0:r1].long()))
+        for k0 in range(0, k, 63):
+            kr = min(63, k - k0)
+            idx = torch.empty(r1 - r0, kr, dtype=torch.int32, device=dev)
+            N.check(lib.hgnn_topk_metrics(
+                N.ptr(S), r1 - r0, C, ld, N.ptr(no_rel), N.ptr(no_rel), N.ptr(no_rel), kr,
+                N.ptr(idx), N.ptr(scratch[0]), N.ptr(scratch[1]), N.stream_ptr(dev)),
+                "hgnn_topk_metrics")
+            left = (S[:, :C] > -math.inf).sum(1, keepdim=True)   # candidates still unlisted
+            empty = torch.arange(kr, device=dev) >= left
+            at = torch.where(empty, ld - 1, idx).long()    # empty slots point at the padding
+            out_s[r0:r1, k0:k0 + kr] = S.gather(1, at).masked_fill_(empty, -math.inf)
+            out_i[r0:r1, k0:k0 + kr] = idx.masked_fill_(empty, -1)
+            if k0 + kr < k:
+                S.scatter_(1, at, -math.inf)
+    return out_s, out_i.long()
+
+
 def recommend(user_emb: torch.Tensor, post_emb: torch.Tensor, K: int = 10,
               batch_scores: int = 1 << 30, fused: Optional[bool] = None,
-              row_dtype: str = _FP32) -> Tuple[torch.Tensor, torch.Tensor]:
+              row_dtype: str = _FP32, users: Optional[torch.Tensor] = None,
+              exclude=None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Top-K posts for every user row: ``(topk_scores, topk_indices)``, each ``[n_users, k]``,
     k = min(K, n_posts) — the scoring of ``recommend_for_user_inductive`` (inference.py:427-429:
     ``torch.topk(user_emb @ known_post_emb.T, min(K, len(scores)))``) for a whole batch of users
@@ -191,7 +328,20 @@ def recommend(user_emb: torch.Tensor, post_emb: torch.Tensor, K: int = 10,
     for d in (64, 128), K <= 64): one kernel, no score matrix.  ``row_dtype`` as in ``evaluate``:
     "bf16", or ``torch.bfloat16`` tables, ranks the rows rounded to bf16 (the fused kernel on
     bf16 MFMA; other widths and K > 64 on the materialised path over the widened rows), and the
-    returned scores are fp32 scores of the rounded rows."""
+    returned scores are fp32 scores of the rounded rows.
+
+    ``users``: an int tensor ``[n]`` of ``user_emb`` rows (repeats and an empty tensor allowed);
+    output row r is then for ``users[r]``.  ``exclude``: a ``SeenIndex`` (build it once), or an
+    int ``[2, M]`` tensor of (user row, post index) pairs from which one is built for the call:
+    the posts a user has already engaged with never appear in that user's list.  It is keyed by
+    the row of ``user_emb``, not by the position in ``users``.  The fused kernels test the
+    exclusion themselves (hgnn_score_topk_excl, hgnn_score_topk_excl_bf16); the materialised path
+    writes -inf into the scores.  A user with fewer than k posts left gets score -inf and index
+    -1 in the empty slots.  With ``row_dtype="bf16"`` on fp32 tables only the selected users'
+    rows are cast."""
+    if users is not None or exclude is not None:
+        return _recommend_subset(user_emb, post_emb, K, batch_scores, fused, row_dtype, users,
+                                 exclude)
     bf16 = _bf16_rows(user_emb, post_emb, row_dtype, "recommend")
     dev = N.require_device(user_emb, post_emb)
     n, C = int(user_emb.shape[0]), int(post_emb.shape[0])
