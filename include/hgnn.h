@@ -483,6 +483,38 @@ int hgnn_edge_score_fwd_bf16(const uint16_t* U, const uint16_t* P, int32_t d, in
                              float* dU, float* part, float* loss, int32_t* err,
                              hgnn_stream_t stream);
 
+/* ---- zero-packed fp32 rows (HGNN_ZPACK=auto|0|1 in the Python layer; csrc/zpack.h) ------------
+ * A table whose rows are mostly zero bit patterns (a ReLU output), stored as mask + non-zero
+ * values for a gather that reads one row per edge.  d = 64 or 128 only.  Row r sits in a slot of
+ * hgnn_zpack_slot_bytes(d) bytes (d = 128: 640, d = 64: 384; 0 for any other d) at byte r * slot:
+ * bytes [0, 16) the mask (bit c set iff the bit pattern of x[r][c] is non-zero, so -0.0,
+ * denormals and NaN are stored and the format is lossless), bytes [16, 16 + 4 nnz) the stored
+ * values in column order; the rest of the slot is never written. */
+int64_t hgnn_zpack_slot_bytes(int32_t d);
+
+/* Whether a table of table_bytes (unpacked) and width d should be read packed: HGNN_ZPACK=0
+ * never, =1 whenever d is 64 or 128, auto (the default): d is 64 or 128, the table is at least
+ * 1 GiB and relu_out says it is a fused-ReLU output. */
+int32_t hgnn_zpack_policy(int64_t table_bytes, int32_t d, int32_t relu_out);
+
+/* The streaming pack pass: x [n_rows, d] fp32 (16-byte aligned) -> out, n_rows *
+ * hgnn_zpack_slot_bytes(d) bytes, 128-byte aligned.  hist, if not NULL, is a device array of 6
+ * counters the pass ADDS into: hist[l] counts the rows whose mask + values take l 128-B lines
+ * (1 .. 5).  Other d: HGNN_E_UNSUPPORTED. */
+int hgnn_zpack_rows(const float* x, int64_t n_rows, int32_t d, void* out, int64_t* hist,
+                    hgnn_stream_t stream);
+
+/* hgnn_score_gather2 with the source table x given zero-packed (xz from hgnn_zpack_rows, n_x
+ * slots).  rowvec (P) stays unpacked.  Same lanes, same order of every sum: out is bitwise what
+ * hgnn_score_gather2 writes for the unpacked table.  The cache policy goes by the unpacked size
+ * n_x * d * 4, as there.  d = 64 or 128, else HGNN_E_UNSUPPORTED. */
+int hgnn_score_gather2_zp(const void* xz, int64_t n_x, const float* rowvec, int32_t d,
+                          const int32_t* rowptr, const int32_t* col, const int32_t* rowptr_n,
+                          const int32_t* col_n, int64_t n_rows, const float* cscale, float inv_e,
+                          const int32_t* heavy_rows, const int32_t* heavy_first, int64_t n_heavy,
+                          int64_t n_chunks, int32_t chunk, float* slab, float* out,
+                          hgnn_stream_t stream);
+
 /* ---- neighbour sampling for mini-batches (BASELINE cfg5; no reference counterpart) -----------
  * For each destination dst_ids[i] (rows of a destination-grouped CSR rowptr/col over n_rows):
  * keep all in-neighbours if deg <= fanout (or fanout < 0), else `fanout` distinct neighbour

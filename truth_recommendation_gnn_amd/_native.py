@@ -151,6 +151,12 @@ _SIGS = {
     "hgnn_score_gather2_bf16": (_c_i32, [_p, _c_i64, _p, _c_i32, _p, _p, _p, _p, _c_i64, _p,
                                          ctypes.c_float, _p, _p, _c_i64, _c_i64, _c_i32, _p, _p,
                                          _p]),
+    "hgnn_zpack_slot_bytes": (_c_i64, [_c_i32]),
+    "hgnn_zpack_policy": (_c_i32, [_c_i64, _c_i32, _c_i32]),
+    "hgnn_zpack_rows": (_c_i32, [_p, _c_i64, _c_i32, _p, _p, _p]),
+    "hgnn_score_gather2_zp": (_c_i32, [_p, _c_i64, _p, _c_i32, _p, _p, _p, _p, _c_i64, _p,
+                                       ctypes.c_float, _p, _p, _c_i64, _c_i64, _c_i32, _p, _p,
+                                       _p]),
     "hgnn_edge_score_fwd_bf16": (_c_i32, [_p, _p, _c_i32, _c_i64, _c_i64, _p, _p, _p, _p, _p,
                                           _c_i64, _p, _p, _p, _p, _p, _p]),
     "hgnn_uniform_i32": (_c_i32, [_p, _c_i64, _c_i32, _p, _p]),

@@ -26,7 +26,11 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall",
 # per-source extra flags: the split-once K3 kernels are vector-issue-bound beside their MFMAs,
 # where SLP-packed v_pk_add_f32 costs more than two scalar adds (MI355X_MICROARCH.md; A/B at the
 # cfg4 shapes: 9M-row backward 3.65 -> 3.62 ms at K = 256, 3.88 -> 3.83 ms at K = 128)
-FILE_FLAGS = {"linear_xs": ["-fno-slp-vectorize"]}
+# The zero-packed dP gather is vector-issue-bound too (its mask arithmetic and selects): the SLP
+# vectorizer paired the rounds' dot products into v_pk_fma_f32 at the cost of a v_mov per operand,
+# 26.5 ms against 24.0 ms without it at cfg4; the other gathers of the file measure the same
+# either way (they wait on memory).
+FILE_FLAGS = {"linear_xs": ["-fno-slp-vectorize"], "gather": ["-fno-slp-vectorize"]}
 
 
 def _sources():

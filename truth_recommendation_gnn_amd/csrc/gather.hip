@@ -13,6 +13,7 @@
 // than `chunk` edges (power-law heads) are split by the plan into chunk-sized items whose
 // partial sums go to a slab, then k_fixup adds them in chunk order.
 #include "hgnn_common.h"
+#include "zpack.h"
 
 // Cache policy of the gathered rows and the output rows (set per launch from the table sizes,
 // `nt_policy` / `hot_policy` below): nt loads / stores when the table is far larger than the
@@ -55,10 +56,134 @@ struct GatherArgs {
   const int32_t* col2;
   int32_t hot;                 // col holds hot flags in bit 31 (hgnn_hot_cols): two-policy loads
   int32_t bf16;                // x (and rowvec) hold bf16 rows: the XT = uint16_t instantiations
+  int32_t zp;                  // x holds zero-packed fp32 rows (zpack.h): the ZP instantiations
 };
 
 // bit 31 of a col_hot entry: the source row is one of the relation's H most referenced rows
 constexpr int32_t kHotIdMask = 0x7fffffff;
+
+// 16 B at a 4-byte-aligned address (a zero-packed row's values): one dwordx4 load.  NT is a
+// template flag here, not GatherArgs::nt_load read in the loop: with both forms of one load in
+// an if / else the compiler merged them into a single plain load (no nt in the ISA).
+typedef uint32_t zp_u4 __attribute__((ext_vector_type(4)));
+typedef zp_u4 zp_u4_a4 __attribute__((aligned(4)));
+template <bool NT>
+__device__ __forceinline__ uint4 zp_load16(const char* p) {
+  zp_u4 v;
+  if constexpr (NT) v = __builtin_nontemporal_load(reinterpret_cast<const zp_u4_a4*>(p));
+  else v = *reinterpret_cast<const zp_u4_a4*>(p);
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+// a DPP move of an integer; lanes without a source lane, and the rows outside ROWS, get 0
+template <int CTRL, int ROWS>
+__device__ __forceinline__ uint32_t dpp_u32(uint32_t x) {
+  // (all rows: bound_ctrl zeroes the lanes without a source and no register has to be cleared
+  // first; a row mask keeps `old`, which then has to be the zero)
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, ROWS, 0xF, ROWS == 0xF);
+}
+
+// How a lane of the ZP gather gets a row's mask: it loads only the mask word its own columns are
+// in (one register per row in flight, a dword request), and the set bits of the row's words
+// before that one come from the other lanes of the slot, which hold those words: the popcount
+// moved up by 8 lanes inside a 16-lane DPP row (row_shr:8) and, in a 32-lane slot, the first
+// row's total broadcast into the second (row_bcast:15 into rows 1 and 3).  Measured against every
+// lane loading the whole 16-B mask (zpack::lane_read; a dwordx4 request per row, four registers)
+// at cfg4: 27.3 ms against 31.4 - 35.9 ms for the gather, DESIGN.md section 5.
+template <int LPR>
+struct ZpMask {
+  static __device__ __forceinline__ uint32_t load(const char* slot, int sl) {
+    // default policy, never nt: the row's first line is wanted again at once, by the value loads
+    return *reinterpret_cast<const uint32_t*>(slot + 4 * zpack::mask_word(sl));
+  }
+  static __device__ __forceinline__ zpack::LaneRead read(uint32_t mw, int sl) {
+    const uint32_t c = zpack::popc(mw);
+    const uint32_t up = dpp_u32<0x118, 0xF>(c);              // row_shr:8
+    uint32_t below = up;
+    if constexpr (LPR == 32) below += dpp_u32<0x142, 0xA>(c + up);   // row_bcast:15, rows 1, 3
+    return zpack::lane_read_word(mw, below, sl);
+  }
+};
+
+// segment_sum over zero-packed source rows (score mode, fp32, one float4 per lane: d = 64 or
+// 128).  The lane layout, the edges of a round and every sum are segment_sum's: lane sl of a
+// slot owns columns 4 sl .. 4 sl + 3, and what it feeds to the dot product and the fmas is the
+// unpacked row's float4 bit for bit (zpack::expand), so the result is bitwise the same.
+//
+// Per row a lane makes two loads, both unconditional: its mask word (ZpMask) and 16 B of values
+// at an offset taken from the mask (nt where the unpacked kernel's row loads are).  An edge slot
+// past the segment's end reads row 0 (col of an idle lane is 0) with its nibble forced to 0; an
+// offset is in the slot for any mask (zpack.h).  The masks of the next round (of the next
+// 64-edge batch after a batch's last round) are requested right after this round's values, so
+// the mask -> value dependency is exposed once per item, not once per round.
+template <int LPR, int UNROLL, bool NT>
+__device__ __forceinline__ void segment_sum_zp(const GatherArgs& a, const int32_t* col, int score,
+                                               int64_t beg, int64_t end, const float4& rv,
+                                               float4& acc) {
+  using V = Vec<4>;
+  using MK = ZpMask<LPR>;
+  constexpr int NS = 64 / LPR;
+  constexpr int R = NS * UNROLL;   // edges per round
+  static_assert(64 % R == 0, "a round never crosses a 64-edge batch");
+  if (beg >= end) return;
+  const int lane = threadIdx.x & 63;
+  const int slot = lane / LPR, sl = lane % LPR;
+  const char* xb = static_cast<const char*>(a.x);
+  const int64_t S = zpack::slot_bytes(a.d);
+  int cidx = lane < end - beg ? col[beg + lane] : 0;
+  uint32_t m[UNROLL];
+  int src[UNROLL];
+#pragma unroll
+  for (int u = 0; u < UNROLL; ++u) {
+    src[u] = __shfl(cidx, u * NS + slot, 64);
+    m[u] = MK::load(xb + (int64_t)src[u] * S, sl);
+  }
+  for (int64_t base = beg; base < end; base += 64) {
+    const int n = (int)min<int64_t>(64, end - base);
+    const int64_t left = end - base - 64;   // edges of the batches after this one
+    const int cnext = lane < left ? col[base + 64 + lane] : 0;
+    for (int j = 0; j < n; j += R) {
+      uint4 t[UNROLL];
+      uint32_t nib[UNROLL];
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        const int e = j + u * NS + slot;
+        const zpack::LaneRead L = MK::read(m[u], sl);
+        nib[u] = e < n ? L.nib : 0u;
+        t[u] = zp_load16<NT>(xb + (int64_t)src[u] * S + zpack::value_byte(L.pre));
+      }
+      const bool same = j + R < n;            // (wave-uniform) the next round is in this batch
+      const int csel = same ? cidx : cnext;
+      const int j0 = same ? j + R : 0;
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        src[u] = __shfl(csel, (j0 + u * NS + slot) & 63, 64);
+        m[u] = MK::load(xb + (int64_t)src[u] * S, sl);
+      }
+      float4 v[UNROLL];
+      float we[UNROLL];
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        uint32_t c[4];
+        zpack::expand(t[u].x, t[u].y, t[u].z, t[u].w, nib[u], c);
+        v[u] = make_float4(__uint_as_float(c[0]), __uint_as_float(c[1]), __uint_as_float(c[2]),
+                           __uint_as_float(c[3]));
+      }
+      const float cw = score == 1 ? *a.cscale * a.inv_e : a.inv_e;
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) {
+        float sdot = 0.f;
+        sdot += V::dot(rv, v[u]);
+        sdot = slot_sum<LPR>(sdot);
+        const float sg = sigmoid_t(sdot, exp_neg_abs(sdot));
+        we[u] = cw * (score == 1 ? sg - 1.f : sg);
+      }
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) V::fma(acc, we[u], v[u]);
+    }
+    cidx = cnext;
+  }
+}
 
 // Sum of row segment [beg, end) of `col` into acc (per lane: VPL vectors of width W; each slot of
 // LPR lanes holds its own partial sum, combined by slot_combine).  SC: the weight of each edge is
@@ -75,13 +200,20 @@ constexpr int32_t kHotIdMask = 0x7fffffff;
 // XT: the source table's element type (RowSrc).  A bf16 row is read 16 B per lane, so d = 128 is
 // 16 lanes per row and 4 rows per wave load; its vectors stay packed while in flight and are
 // widened to fp32 where they are summed.  Everything after the load is fp32 either way.
-template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC, bool HOT, typename XT = float>
+template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC, bool HOT, typename XT = float,
+          int ZP = 0>
 __device__ __forceinline__ void segment_sum(const GatherArgs& a, const int32_t* col, int score,
                                             int64_t beg, int64_t end,
                                             const typename Vec<W>::T (&rv)[VPL],
                                             typename Vec<W>::T (&acc)[VPL]) {
   using V = Vec<W>;
   using S = RowSrc<XT, W>;
+  if constexpr (ZP != 0) {
+    static_assert(SC && !HAS_W && !HOT && VPL == 1 && W == 4 && sizeof(XT) == 4,
+                  "zero-packed rows: the fp32 score gather at d = 64 / 128");
+    segment_sum_zp<LPR, UNROLL, ZP == 2>(a, col, score, beg, end, rv[0], acc[0]);
+    return;
+  }
   constexpr int NS = 64 / LPR;
   const int lane = threadIdx.x & 63;
   const int slot = lane / LPR, sl = lane % LPR;
@@ -158,7 +290,7 @@ __device__ __forceinline__ void slot_combine(typename Vec<W>::T (&acc)[VPL]) {
 
 // one item (a light row, or a chunk of a heavy row) per wave
 template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC, bool HOT = false,
-          typename XT = float>
+          typename XT = float, int ZP = 0>
 __device__ __forceinline__ void gather_item(const GatherArgs& a, const int64_t item) {
   using V = Vec<W>;
   using S = RowSrc<XT, W>;
@@ -204,10 +336,11 @@ __device__ __forceinline__ void gather_item(const GatherArgs& a, const int64_t i
                 : V::zero();
   }
   if (own)
-    segment_sum<LPR, VPL, W, UNROLL, HAS_W, SC, HOT, XT>(a, a.col, a.score, beg, end, rv, acc);
+    segment_sum<LPR, VPL, W, UNROLL, HAS_W, SC, HOT, XT, ZP>(a, a.col, a.score, beg, end, rv,
+                                                             acc);
   if (two && !partial)
-    segment_sum<LPR, VPL, W, UNROLL, HAS_W, SC, false, XT>(a, a.col2, 2, a.rowptr2[row],
-                                                           a.rowptr2[row + 1], rv, acc);
+    segment_sum<LPR, VPL, W, UNROLL, HAS_W, SC, false, XT, ZP>(a, a.col2, 2, a.rowptr2[row],
+                                                               a.rowptr2[row + 1], rv, acc);
   slot_combine<LPR, VPL, W>(acc);
   if (!writer) return;
   float s = 1.f;
@@ -236,6 +369,17 @@ __global__ void __launch_bounds__(256) k_gather(const GatherArgs a) {
   const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (item >= a.n_items) return;
   gather_item<LPR, VPL, W, UNROLL, HAS_W, SC, HOT, XT>(a, item);
+}
+
+// The ZP gather as its own kernel (ZP = 1, or 2 with nt value loads): it holds a round's loaded
+// words and the next round's masks at once, and left to itself the register allocator spent
+// 112 VGPRs on it (4 waves per SIMD); asked for 6 waves it fits without a spill in the loop.
+template <int LPR, int UNROLL, int ZP>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
+k_gather_zp(const GatherArgs a) {
+  const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (item >= a.n_items) return;
+  gather_item<LPR, 1, 4, UNROLL, false, true, false, float, ZP>(a, item);
 }
 
 // Several gathers of one row width in one launch (hgnn_gather_reduce_multi): job j owns the
@@ -329,8 +473,27 @@ static int launch_gather(const GatherArgs& a, bool has_w, hipStream_t stream) {
   return check_launch("k_gather");
 }
 
+// zero-packed source rows: the score gather's d = 64 / d = 128 forms (their lane layouts and
+// depths), nothing else
+static int dispatch_gather_zp(const GatherArgs& a, hipStream_t stream) {
+  if (!a.score || !zpack::width_ok(a.d))
+    return fail(HGNN_E_UNSUPPORTED, "gather(zero-packed rows): score mode at d = 64 or 128 (d=%d)",
+                a.d);
+  const dim3 grid((unsigned)cdiv(a.n_items, 4)), block(256);
+#define HGNN_GZP(LPR, ZP) \
+  hipLaunchKernelGGL((k_gather_zp<LPR, 4, ZP>), grid, block, 0, stream, a)
+  if (a.d == 64) {
+    if (a.nt_load) HGNN_GZP(16, 2); else HGNN_GZP(16, 1);
+  } else {
+    if (a.nt_load) HGNN_GZP(32, 2); else HGNN_GZP(32, 1);
+  }
+#undef HGNN_GZP
+  return check_launch("k_gather(zp)");
+}
+
 static int dispatch_gather(const GatherArgs& a, bool has_w, hipStream_t stream) {
   const int d = a.d;
+  if (a.zp) return dispatch_gather_zp(a, stream);
   if (d % 4 == 0) {
     const int nv = d / 4;  // float4 vectors per row
     if (nv <= 4) return launch_gather<4, 1, 4, 4>(a, has_w, stream);
@@ -660,6 +823,27 @@ int hgnn_score_gather2(const float* x, int64_t n_x, const float* rowvec, int32_t
   a.rowvec = rowvec; a.cscale = cscale; a.inv_e = inv_e; a.score = 1;
   a.rowptr2 = rowptr_n; a.col2 = col_n;
   nt_policy(a, n_x);
+  return run_gather(a, as_stream(stream));
+}
+
+int hgnn_score_gather2_zp(const void* xz, int64_t n_x, const float* rowvec, int32_t d,
+                          const int32_t* rowptr, const int32_t* col, const int32_t* rowptr_n,
+                          const int32_t* col_n, int64_t n_rows, const float* cscale, float inv_e,
+                          const int32_t* heavy_rows, const int32_t* heavy_first, int64_t n_heavy,
+                          int64_t n_chunks, int32_t chunk, float* slab, float* out,
+                          hgnn_stream_t stream) {
+  if (!zpack::width_ok(d))
+    return fail(HGNN_E_UNSUPPORTED, "score_gather2_zp: d=%d (zero-packed rows: 64 or 128)", d);
+  if (!rowptr_n && n_rows > 0) return fail(HGNN_E_ARG, "score_gather2_zp: rowptr_n is null");
+  GatherArgs a{};
+  a.x = xz; a.rowptr = rowptr; a.col = col;
+  a.heavy_rows = heavy_rows; a.heavy_first = heavy_first; a.slab = slab; a.out = out;
+  a.n_rows = n_rows; a.n_heavy = n_heavy; a.n_items = n_rows + (n_heavy > 0 ? n_chunks : 0);
+  a.d = d; a.chunk = chunk;
+  a.rowvec = rowvec; a.cscale = cscale; a.inv_e = inv_e; a.score = 1;
+  a.rowptr2 = rowptr_n; a.col2 = col_n;
+  a.zp = 1;
+  nt_policy(a, n_x);   // by the size of the unpacked table: the policy of hgnn_score_gather2
   return run_gather(a, as_stream(stream));
 }
 

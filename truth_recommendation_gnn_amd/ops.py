@@ -447,6 +447,40 @@ def gather_mean_many(pairs: Sequence[Tuple[torch.Tensor, RelationCSR]],
     return [o for _, _, o in jobs]
 
 
+# ----------------------------------------------------------------------------- zero-packed rows
+# A K3 output that went through the fused ReLU carries this attribute (set True where such
+# outputs are produced, ``linear_fwd`` / ``linear_fwd_many``).  It is a hint about sparsity and
+# nothing else: the packed format is lossless (``csrc/zpack.h``), so a stale mark on a tensor
+# somebody wrote into afterwards costs time, never a wrong result.
+RELU_OUT = "_hgnn_relu_out"
+
+
+def zpack_on(x: torch.Tensor, relu_out: bool) -> bool:
+    """Whether the loss's dP gather reads ``x`` zero-packed: ``HGNN_ZPACK`` = ``0`` never, ``1``
+    whenever the width is 64 or 128, ``auto`` (the default) for a fused-ReLU K3 output of at
+    least 1 GiB with such a width (``hgnn_zpack_policy``, read per call)."""
+    return bool(N.lib().hgnn_zpack_policy(_table_bytes(x), int(x.shape[1]), 1 if relu_out else 0))
+
+
+def zpack_rows(x: torch.Tensor, hist: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The zero-packed copy of an fp32 table of width 64 or 128 (``hgnn_zpack_rows``): a uint8
+    tensor of ``n * hgnn_zpack_slot_bytes(d)`` bytes, per row a 16-B mask and the non-zero bit
+    patterns; the rest of each slot stays unwritten.  ``hist`` (6 int64 counters on the device)
+    has the rows counted into it by the 128-B lines they take."""
+    x = _check_f32(x, "zpack_rows")
+    dev = N.require_device(x)
+    n, d = int(x.shape[0]), int(x.shape[1])
+    slot = int(N.lib().hgnn_zpack_slot_bytes(d))
+    if slot == 0:
+        raise ValueError(f"zpack_rows: d={d}; zero-packed rows are 64 or 128 wide")
+    out = torch.empty(n * slot, dtype=torch.uint8, device=dev)
+    # (bytes: the table read and, the sparsity unknown here, mask + every value written)
+    with _timed(f"zpack[{n}]x{d}", n * (4 * d + 16 + 4 * d)):
+        N.check(N.lib().hgnn_zpack_rows(N.ptr(x), n, d, N.ptr(out), N.ptr(hist),
+                                        N.stream_ptr(dev)), "hgnn_zpack_rows")
+    return out
+
+
 def _table_bytes(x: torch.Tensor) -> int:
     return x.numel() * x.element_size()
 
@@ -512,9 +546,11 @@ def _score_gather(U, P, grouped, mode, cscale, inv_e, out, accumulate, tag):
             N.stream_ptr(dev)), "hgnn_score_gather")
 
 
-def _score_gather2(U, P, pos, negs, cscale, inv_e, out):
+def _score_gather2(U, P, pos, negs, cscale, inv_e, out, Uz=None):
     """Both dP gathers in one pass (hgnn_score_gather2): row r sums its positive edges (mode 1,
-    heavy-row plan) and its negatives (mode 2) into one accumulator and writes dP[r] once."""
+    heavy-row plan) and its negatives (mode 2) into one accumulator and writes dP[r] once.
+    ``Uz``: ``zpack_rows(U)``; the gather then reads the packed rows (same sums, bit for bit;
+    the timer entry keeps its name and the unpacked table's algorithmic bytes)."""
     p = pos.plan
     dev = out.device
     d = int(out.shape[1])
@@ -533,6 +569,13 @@ def _score_gather2(U, P, pos, negs, cscale, inv_e, out):
                 N.ptr(negs.rowptr), N.ptr(negs.col), n, N.ptr(cscale), inv_e,
                 N.ptr(p.heavy_rows), N.ptr(p.heavy_first), p.n_heavy, p.n_chunks, p.chunk,
                 N.ptr(slab), N.ptr(out), N.stream_ptr(dev)), "hgnn_score_gather2_bf16")
+            return
+        if Uz is not None:
+            N.check(N.lib().hgnn_score_gather2_zp(
+                N.ptr(Uz), U.shape[0], N.ptr(P), d, N.ptr(pos.rowptr), N.ptr(pos.col),
+                N.ptr(negs.rowptr), N.ptr(negs.col), n, N.ptr(cscale), inv_e,
+                N.ptr(p.heavy_rows), N.ptr(p.heavy_first), p.n_heavy, p.n_chunks, p.chunk,
+                N.ptr(slab), N.ptr(out), N.stream_ptr(dev)), "hgnn_score_gather2_zp")
             return
         N.check(N.lib().hgnn_score_gather2(
             N.ptr(U), U.shape[0], N.ptr(P), d, N.ptr(pos.rowptr), N.ptr(pos.col),
@@ -615,6 +658,8 @@ def linear_fwd(segs: Sequence[torch.Tensor], w: torch.Tensor, b: Optional[torch.
                                              N.ptr(w), h, N.ptr(b), N.ptr(add),
                                              1 if relu else 0, N.ptr(out), N.ptr(mask_out),
                                              N.stream_ptr(w.device)), "hgnn_linear_fwd_mask")
+    if relu:
+        setattr(out, RELU_OUT, True)
     return out
 
 
@@ -717,6 +762,9 @@ def linear_fwd_many(jobs) -> List[torch.Tensor]:
             N.ptr_array([j.w for j in jobs]), h, N.ptr_array([j.b for j in jobs]),
             N.int_array([1 if j.relu else 0 for j in jobs]), N.ptr_array(outs),
             N.ptr_array([j.mask for j in jobs]), N.stream_ptr(dev)), "hgnn_linear_fwd_multi")
+    for j, o in zip(jobs, outs):
+        if j.relu:
+            setattr(o, RELU_OUT, True)
     return outs
 
 
@@ -1590,6 +1638,7 @@ def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total:
     and in the dP gather; loss, dU and dP stay fp32).  The sharded step's arguments (``ready``,
     ``on_dP``, ``p_chunks``) are for fp32 rows only."""
     bf16 = U.dtype == torch.bfloat16
+    relu_out = bool(getattr(U, RELU_OUT, False))   # (read here: .contiguous() may copy)
     if bf16:
         if P.dtype != torch.bfloat16:
             raise TypeError("edge_bce_loss: bf16 rows need both tables in bfloat16")
@@ -1658,7 +1707,13 @@ def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total:
     else:
         # (Measured and not kept, round 5: this gather in 8 source-block passes like K1,
         # 32.83 vs 31.32 ms at cfg4 — each pass re-reads its rows' P vectors and dP.)
-        _score_gather2(U, P, pf, negs, c, inv_e, dP)
+        # A large post-ReLU U is more than half zeros: packed once (one streaming pass), the
+        # gather's 2 E row reads fetch mask + non-zeros only (HGNN_ZPACK, csrc/zpack.h).
+        Uz = None
+        if not bf16 and ready is None and zpack_on(U, relu_out):
+            Uz = zpack_rows(U)
+        _score_gather2(U, P, pf, negs, c, inv_e, dP, Uz)
+        del Uz
     if on_dP is not None:
         on_dP(dP)
     if ready is not None and p_chunks is not None:
