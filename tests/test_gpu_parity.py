@@ -67,7 +67,7 @@ def test_skew_plan_matches_reference_plan():
 
 
 # ----------------------------------------------------------------------------- K1 / K2
-@pytest.mark.parametrize("d", [1, 3, 4, 7, 16, 64, 100, 128, 256, 300])
+@pytest.mark.parametrize("d", [1, 3, 4, 7, 16, 32, 33, 64, 100, 128, 130, 256, 300, 513, 520])
 @pytest.mark.parametrize("chunk", [None, 8])
 def test_gather_mean_matches_oracle(d, chunk):
     rng = np.random.default_rng(d)
@@ -78,6 +78,18 @@ def test_gather_mean_matches_oracle(d, chunk):
     csr = graph.RelationCSR(ei.to(DEV), n_src, n_dst, chunk=chunk)
     got = ops.gather_mean(x.to(DEV), csr)
     close(got, ref)
+
+
+@pytest.mark.parametrize("d", [1025, 1028])
+def test_gather_mean_above_1024_columns_is_unsupported(d):
+    """Past the last row of either fp32 width table (scalar rows, float4 rows): an error that
+    names the width, never a launch."""
+    from truth_recommendation_gnn_amd import _native as Nn
+    rng = np.random.default_rng(d)
+    ei = rand_coo(rng, 20, 10, 60, skew=False)
+    csr = graph.RelationCSR(ei.to(DEV), 20, 10)
+    with pytest.raises(Nn.NativeError, match=r"code 1004.*d=%d" % d):
+        ops.gather_mean(torch.zeros(20, d, device=DEV), csr)
 
 
 @pytest.mark.parametrize("d", [3, 64, 128])
@@ -817,6 +829,34 @@ def test_loss_dp_gather_in_row_blocks_is_bitwise_one_pass(neg_kind):
             assert torch.equal(x, y)
 
 
+def test_loss_callbacks_come_in_the_order_the_sharded_step_overlaps():
+    """What edge_bce_loss_raw calls back, in order: without p_chunks ``ready`` (after the
+    negatives sort, before anything reads P) then ``on_dP``; with p_chunks each block's
+    ``ready_fn`` before that block's gather, ``on_dP`` once dP is enqueued, and ``ready`` last,
+    before the scoring pass."""
+    rng = np.random.default_rng(33)
+    nu, npost, E, d = 400, 250, 5000, 64
+    pos = torch.from_numpy(np.stack([rng.integers(0, nu, E),
+                                     rng.integers(0, npost, E)]).astype(np.int64)).to(DEV)
+    U = torch.from_numpy(rng.standard_normal((nu, d)).astype(np.float32) * 0.3).to(DEV)
+    P = torch.from_numpy(rng.standard_normal((npost, d)).astype(np.float32) * 0.3).to(DEV)
+    cscale = torch.tensor(1.25, device=DEV)
+    neg = ops.sample_negatives(pos, npost, generator=torch.Generator(device=DEV).manual_seed(4))
+    calls = []
+    ready = lambda: calls.append("ready")
+    on_dP = lambda dP: calls.append("on_dP")
+    chunks = [(0, 120, lambda: calls.append("chunk0")),
+              (120, npost, lambda: calls.append("chunk1"))]
+    blocked = ops.edge_bce_loss_raw(U, P, pos, neg, E, cscale, ready=ready, on_dP=on_dP,
+                                    p_chunks=chunks)
+    assert calls == ["chunk0", "chunk1", "on_dP", "ready"]
+    del calls[:]
+    plain = ops.edge_bce_loss_raw(U, P, pos, neg, E, cscale, ready=ready, on_dP=on_dP)
+    assert calls == ["ready", "on_dP"]
+    for x, y in zip(blocked, plain):
+        assert torch.equal(x, y)
+
+
 @pytest.mark.parametrize("nu,npost,E,d", [(3000, 1 << 20, 70_001, 128), (500, 37, 9_000, 64),
                                            (10, 5, 0, 16)])
 def test_edge_score_draw_entry_equals_materialised_draws(nu, npost, E, d):
@@ -1237,7 +1277,7 @@ def test_k3_split_matches_f32_kernels_closely():
         assert float((a - c).abs().max()) <= 2e-5 * scale, (float((a - c).abs().max()), scale)
 
 
-@pytest.mark.parametrize("d", [128, 64, 16])
+@pytest.mark.parametrize("d", [128, 64, 16, 32, 256, 512])
 def test_gather_multi_equals_single_calls(d):
     """hgnn_gather_reduce_multi (a sampled layer's K1s, or one round of its K2s, as one launch;
     round 6) against one hgnn_gather_reduce per job: the mean gathers into fresh outputs and the

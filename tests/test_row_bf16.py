@@ -11,7 +11,7 @@ The graph is the one of test_hot_rows.py, built the same way: 300 destination ro
 Zipf-drawn source rows, degrees forced to 0, 64, 65, 700 and 300 at chunk 64 (an empty row, both
 sides of the 64-edge index chunk, three heavy rows, one of them above ``acc_limit`` = 150).
 Widths: 8 (one 16-B vector per row), 64 and 128 (the product's), 264 (33 vectors: the
-past-the-row guards)."""
+past-the-row guards), and 32, 256 and 520 for the remaining rows of the bf16 width table."""
 import os
 import pathlib
 import subprocess
@@ -28,7 +28,7 @@ ROOT = pathlib.Path(__file__).resolve().parents[1]
 N_DST, N_SRC = 300, 50
 CHUNK = 64
 ACC_LIMIT = 150
-DS = (8, 64, 128, 264)
+DS = (8, 32, 64, 128, 256, 264, 520)
 LOSS_DS = (64, 128)
 HGNN_E_ARG, HGNN_E_UNSUPPORTED = 1001, 1004
 

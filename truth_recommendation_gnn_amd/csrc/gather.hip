@@ -455,30 +455,85 @@ __global__ void __launch_bounds__(256) k_fixup(const GatherArgs a) {
   }
 }
 
-template <int LPR, int VPL, int W, int UNROLL>
-static int launch_gather(const GatherArgs& a, bool has_w, hipStream_t stream) {
+// ---------------------------------------------------------------------------------- host half
+// Every entry point is its own argument rules, gather_args (+ score_args / hot_args), run_gather;
+// run_gather validates, derives the Variant once and launches from the element type's width table.
+enum class Variant { kScore, kHotWeighted, kHot, kWeighted, kPlain };
+
+// One row of a width table: the lane layout and the rows in flight per slot (the depth) per
+// variant: UM the mean / plain sum, UW weighted, US the score gather.
+template <int LPR_, int VPL_, int W_, int UM_, int UW_, int US_>
+struct Shape {
+  static constexpr int LPR = LPR_, VPL = VPL_, W = W_, UM = UM_, UW = UW_, US = US_;
+};
+
+// The fp32 row widths: f(Shape) for the row that takes d (k_gather and k_gather_multi).
+template <typename F>
+static int with_shape_f32(int d, F&& f) {
+  if (d % 4 == 0) {
+    const int nv = d / 4;  // float4 vectors per row
+    if (nv <= 4) return f(Shape<4, 1, 4, 4, 4, 4>{});
+    if (nv <= 8) return f(Shape<8, 1, 4, 4, 4, 4>{});
+    // d = 64: rows in flight per wave (4 x the depth) chosen per variant on cfg2 (MI355X).  The
+    // mean gathers take 32: user rows average 20 edges, so one round of loads covers most of
+    // them (user<-post 0.84 -> 0.80 ms); the weighted K2 24 (0.50 -> 0.485 ms); the score
+    // gather keeps 16 (its dot products hold more registers: 1.39 ms at 16, 1.50 at 32).
+    if (nv <= 16) return f(Shape<16, 1, 4, 8, 6, 4>{});
+    // d = 128 (512-B rows): 8, 12 or 16 rows in flight measured the same on cfg3 and cfg4; 8
+    // kept (the 12- and 16-deep forms are no longer built)
+    if (nv <= 32) return f(Shape<32, 1, 4, 4, 4, 4>{});
+    if (nv <= 64) return f(Shape<64, 1, 4, 4, 4, 4>{});
+    if (nv <= 128) return f(Shape<64, 2, 4, 2, 2, 2>{});
+    if (nv <= 256) return f(Shape<64, 4, 4, 2, 2, 2>{});
+  } else {
+    if (d <= 16) return f(Shape<16, 1, 1, 4, 4, 4>{});
+    if (d <= 64) return f(Shape<64, 1, 1, 4, 4, 4>{});
+    if (d <= 256) return f(Shape<64, 4, 1, 2, 2, 2>{});
+    if (d <= 1024) return f(Shape<64, 16, 1, 1, 1, 1>{});
+  }
+  return fail(HGNN_E_UNSUPPORTED, "gather: d=%d > 1024", d);
+}
+
+// bf16 source rows (W = 8, 16 B per lane; d % 8 == 0 and d <= 1024, bf16_width_rule).
+// The depths are the fp32 kernels' rows in flight at the same d (d = 64: 32 / 24 / 16 rows,
+// d = 128: 8).  At d = 128 twice that (16 rows, the fp32 kernel's BYTES in flight) measured the
+// same at cfg4 (K1 post<-user 7.64 - 7.77 ms at 8 rows, 7.58 - 7.59 at 16; the dP gather 15.73 -
+// 15.99 against 15.68 - 16.28; the step 89.7 - 90.0 against 89.0 - 90.1 ms): 8 kept, the form
+// with fewer registers held; the deeper one is no longer built (DESIGN.md section 5).
+template <typename F>
+static int with_shape_bf16(int d, F&& f) {
+  const int nv = d / 8;  // 16-B vectors per row
+  if (nv <= 2) return f(Shape<2, 1, 8, 2, 2, 2>{});
+  if (nv <= 4) return f(Shape<4, 1, 8, 4, 4, 4>{});
+  if (nv <= 8) return f(Shape<8, 1, 8, 4, 3, 2>{});
+  if (nv <= 16) return f(Shape<16, 1, 8, 2, 2, 2>{});
+  if (nv <= 32) return f(Shape<32, 1, 8, 4, 4, 4>{});
+  if (nv <= 64) return f(Shape<64, 1, 8, 4, 4, 4>{});
+  return f(Shape<64, 2, 8, 2, 2, 2>{});
+}
+
+// The five variants of one table row over XT rows (float, or uint16_t for bf16).
+template <typename XT, int LPR, int VPL, int W, int UM, int UW, int US>
+static int launch_gather(Shape<LPR, VPL, W, UM, UW, US>, const GatherArgs& a, Variant v,
+                         hipStream_t stream) {
   const dim3 grid((unsigned)cdiv(a.n_items, 4)), block(256);
-  if (a.score)
-    hipLaunchKernelGGL((k_gather<LPR, VPL, W, UNROLL, false, true>), grid, block, 0, stream, a);
-  else if (a.hot && has_w)   // the two-policy loads as their own instantiations (hot_policy)
-    hipLaunchKernelGGL((k_gather<LPR, VPL, W, UNROLL, true, false, true>), grid, block, 0, stream,
-                       a);
-  else if (a.hot)
-    hipLaunchKernelGGL((k_gather<LPR, VPL, W, UNROLL, false, false, true>), grid, block, 0,
-                       stream, a);
-  else if (has_w)
-    hipLaunchKernelGGL((k_gather<LPR, VPL, W, UNROLL, true>), grid, block, 0, stream, a);
-  else
-    hipLaunchKernelGGL((k_gather<LPR, VPL, W, UNROLL, false>), grid, block, 0, stream, a);
-  return check_launch("k_gather");
+#define HGNN_G(U, HAS_W, SC, HOT) \
+  hipLaunchKernelGGL((k_gather<LPR, VPL, W, U, HAS_W, SC, HOT, XT>), grid, block, 0, stream, a)
+  switch (v) {
+    case Variant::kScore: HGNN_G(US, false, true, false); break;
+    // the two-policy loads as their own instantiations (hot_policy)
+    case Variant::kHotWeighted: HGNN_G(UW, true, false, true); break;
+    case Variant::kHot: HGNN_G(UM, false, false, true); break;
+    case Variant::kWeighted: HGNN_G(UW, true, false, false); break;
+    case Variant::kPlain: HGNN_G(UM, false, false, false); break;
+  }
+#undef HGNN_G
+  return check_launch(sizeof(XT) == 2 ? "k_gather(bf16)" : "k_gather");
 }
 
 // zero-packed source rows: the score gather's d = 64 / d = 128 forms (their lane layouts and
-// depths), nothing else
-static int dispatch_gather_zp(const GatherArgs& a, hipStream_t stream) {
-  if (!a.score || !zpack::width_ok(a.d))
-    return fail(HGNN_E_UNSUPPORTED, "gather(zero-packed rows): score mode at d = 64 or 128 (d=%d)",
-                a.d);
+// depths), nothing else (run_score2 alone sets GatherArgs::zp, after its width rule)
+static int launch_gather_zp(const GatherArgs& a, hipStream_t stream) {
   const dim3 grid((unsigned)cdiv(a.n_items, 4)), block(256);
 #define HGNN_GZP(LPR, ZP) \
   hipLaunchKernelGGL((k_gather_zp<LPR, 4, ZP>), grid, block, 0, stream, a)
@@ -491,89 +546,6 @@ static int dispatch_gather_zp(const GatherArgs& a, hipStream_t stream) {
   return check_launch("k_gather(zp)");
 }
 
-static int dispatch_gather(const GatherArgs& a, bool has_w, hipStream_t stream) {
-  const int d = a.d;
-  if (a.zp) return dispatch_gather_zp(a, stream);
-  if (d % 4 == 0) {
-    const int nv = d / 4;  // float4 vectors per row
-    if (nv <= 4) return launch_gather<4, 1, 4, 4>(a, has_w, stream);
-    if (nv <= 8) return launch_gather<8, 1, 4, 4>(a, has_w, stream);
-    if (nv <= 16) {
-      // d = 64: rows in flight per wave (4 x UNROLL) chosen per variant on cfg2 (MI355X).  The
-      // mean gathers take 32: user rows average 20 edges, so one round of loads covers most of
-      // them (user<-post 0.84 -> 0.80 ms); the weighted K2 24 (0.50 -> 0.485 ms); the score
-      // gather keeps 16 (its dot products hold more registers: 1.39 ms at 16, 1.50 at 32).
-      const dim3 grid((unsigned)cdiv(a.n_items, 4)), block(256);
-      if (a.score)
-        hipLaunchKernelGGL((k_gather<16, 1, 4, 4, false, true>), grid, block, 0, stream, a);
-      else if (a.hot && has_w)
-        hipLaunchKernelGGL((k_gather<16, 1, 4, 6, true, false, true>), grid, block, 0, stream, a);
-      else if (a.hot)
-        hipLaunchKernelGGL((k_gather<16, 1, 4, 8, false, false, true>), grid, block, 0, stream, a);
-      else if (has_w)
-        hipLaunchKernelGGL((k_gather<16, 1, 4, 6, true>), grid, block, 0, stream, a);
-      else
-        hipLaunchKernelGGL((k_gather<16, 1, 4, 8, false>), grid, block, 0, stream, a);
-      return check_launch("k_gather");
-    }
-    // d = 128 (512-B rows): 8, 12 or 16 rows in flight measured the same on cfg3 and cfg4; 8
-    // kept (the 12- and 16-deep forms are no longer built)
-    if (nv <= 32) return launch_gather<32, 1, 4, 4>(a, has_w, stream);
-    if (nv <= 64) return launch_gather<64, 1, 4, 4>(a, has_w, stream);
-    if (nv <= 128) return launch_gather<64, 2, 4, 2>(a, has_w, stream);
-    if (nv <= 256) return launch_gather<64, 4, 4, 2>(a, has_w, stream);
-    return fail(HGNN_E_UNSUPPORTED, "gather: d=%d > 1024", d);
-  }
-  if (d <= 16) return launch_gather<16, 1, 1, 4>(a, has_w, stream);
-  if (d <= 64) return launch_gather<64, 1, 1, 4>(a, has_w, stream);
-  if (d <= 256) return launch_gather<64, 4, 1, 2>(a, has_w, stream);
-  if (d <= 1024) return launch_gather<64, 16, 1, 1>(a, has_w, stream);
-  return fail(HGNN_E_UNSUPPORTED, "gather: d=%d > 1024", d);
-}
-
-// bf16 source rows (W = 8, 16 B per lane): the same five variants, rows in flight per wave
-// (64 / LPR x the depth) per variant: UM the mean / plain sum, UW weighted, US the score gather.
-template <int LPR, int VPL, int UM, int UW, int US>
-static int launch_gather_bf16(const GatherArgs& a, bool has_w, hipStream_t stream) {
-  using B = uint16_t;
-  const dim3 grid((unsigned)cdiv(a.n_items, 4)), block(256);
-  if (a.score)
-    hipLaunchKernelGGL((k_gather<LPR, VPL, 8, US, false, true, false, B>), grid, block, 0, stream,
-                       a);
-  else if (a.hot && has_w)
-    hipLaunchKernelGGL((k_gather<LPR, VPL, 8, UW, true, false, true, B>), grid, block, 0, stream,
-                       a);
-  else if (a.hot)
-    hipLaunchKernelGGL((k_gather<LPR, VPL, 8, UM, false, false, true, B>), grid, block, 0, stream,
-                       a);
-  else if (has_w)
-    hipLaunchKernelGGL((k_gather<LPR, VPL, 8, UW, true, false, false, B>), grid, block, 0, stream,
-                       a);
-  else
-    hipLaunchKernelGGL((k_gather<LPR, VPL, 8, UM, false, false, false, B>), grid, block, 0,
-                       stream, a);
-  return check_launch("k_gather(bf16)");
-}
-
-// The depths are the fp32 kernels' rows in flight at the same d (d = 64: 32 / 24 / 16 rows,
-// d = 128: 8).  At d = 128 twice that (16 rows, the fp32 kernel's BYTES in flight) measured the
-// same at cfg4 (K1 post<-user 7.64 - 7.77 ms at 8 rows, 7.58 - 7.59 at 16; the dP gather 15.73 -
-// 15.99 against 15.68 - 16.28; the step 89.7 - 90.0 against 89.0 - 90.1 ms): 8 kept, the form
-// with fewer registers held; the deeper one is no longer built (DESIGN.md section 5).
-static int dispatch_gather_bf16(const GatherArgs& a, bool has_w, hipStream_t stream) {
-  const int d = a.d;
-  if (d % 8 != 0 || d > 1024)
-    return fail(HGNN_E_UNSUPPORTED, "gather(bf16 rows): d=%d (needs d %% 8 == 0 and d <= 1024)", d);
-  const int nv = d / 8;  // 16-B vectors per row
-  if (nv <= 2) return launch_gather_bf16<2, 1, 2, 2, 2>(a, has_w, stream);
-  if (nv <= 4) return launch_gather_bf16<4, 1, 4, 4, 4>(a, has_w, stream);
-  if (nv <= 8) return launch_gather_bf16<8, 1, 4, 3, 2>(a, has_w, stream);
-  if (nv <= 16) return launch_gather_bf16<16, 1, 2, 2, 2>(a, has_w, stream);
-  if (nv <= 32) return launch_gather_bf16<32, 1, 4, 4, 4>(a, has_w, stream);
-  if (nv <= 64) return launch_gather_bf16<64, 1, 4, 4, 4>(a, has_w, stream);
-  return launch_gather_bf16<64, 2, 2, 2, 2>(a, has_w, stream);
-}
-
 // nt above 1 GiB: cfg4's 4.6 GB user table and its 4.6 GB user-side outputs.  Output rows of
 // the dP gather / K2s / means are read by another kernel long after they left L2 (cfg4 step
 // 168.1 -> 167.5 ms with nt stores, mostly the dP gather); cfg2/cfg3 tables stay cache-resident.
@@ -584,6 +556,8 @@ static void nt_policy(GatherArgs& a, int64_t n_x, int64_t elem = 4) {
   a.nt_load = a.score && n_x * a.d * elem >= kNtBytes ? 1 : 0;
   a.nt_store = (a.score ? a.nt_load : a.n_rows * a.d * 4 >= kNtBytes) ? 1 : 0;
 }
+// (a zero-packed table counts by its unpacked size: the policy of hgnn_score_gather2)
+static int64_t elem_bytes(const GatherArgs& a) { return a.bf16 ? 2 : 4; }
 
 // Two-policy loads (col_hot): on when the table outgrows the Infinity Cache (the scoring pass's
 // nt_neg threshold), the caller passed a col_hot, and the flagged rows carry at least half of
@@ -605,7 +579,57 @@ static bool hot_policy(int64_t table_bytes, bool has_col_hot, float hot_share) {
   return table_bytes >= kHotTableBytes && hot_share >= kHotShareMin;
 }
 
-static int run_gather(GatherArgs a, hipStream_t stream) {
+// The fields every gather has: table, grouping, weights, flags, heavy-row plan, slab, out.
+static GatherArgs gather_args(const void* x, int32_t d, const int32_t* rowptr, const int32_t* col,
+                              int64_t n_rows, const float* edge_w, const float* col_w,
+                              const float* row_w, int32_t flags, int64_t acc_limit,
+                              const int32_t* heavy_rows, const int32_t* heavy_first,
+                              int64_t n_heavy, int64_t n_chunks, int32_t chunk, float* slab,
+                              float* out) {
+  GatherArgs a{};
+  a.x = x; a.rowptr = rowptr; a.col = col; a.edge_w = edge_w; a.col_w = col_w; a.row_w = row_w;
+  a.heavy_rows = heavy_rows; a.heavy_first = heavy_first; a.slab = slab; a.out = out;
+  a.n_rows = n_rows; a.n_heavy = n_heavy; a.n_items = n_rows + (n_heavy > 0 ? n_chunks : 0);
+  a.d = d; a.chunk = chunk; a.mean = (flags & HGNN_MEAN) ? 1 : 0;
+  a.accumulate = (flags & HGNN_ACCUMULATE) ? 1 : 0;
+  a.acc_limit = acc_limit;
+  return a;
+}
+
+// score mode: the row's own vectors and the weight mode; optionally the second grouped list
+static void score_args(GatherArgs& a, const void* rowvec, const float* cscale, float inv_e,
+                       int32_t mode, const int32_t* rowptr2 = nullptr,
+                       const int32_t* col2 = nullptr) {
+  a.rowvec = rowvec; a.cscale = cscale; a.inv_e = inv_e; a.score = mode;
+  a.rowptr2 = rowptr2; a.col2 = col2;
+}
+
+// the two-policy loads, where hot_policy wants them: the flagged ids replace col
+static void hot_args(GatherArgs& a, int64_t n_x, const int32_t* col_hot, float hot_share) {
+  if (hot_policy(n_x * (int64_t)a.d * elem_bytes(a), col_hot != nullptr, hot_share)) {
+    a.col = col_hot;
+    a.hot = 1;
+  }
+}
+
+// Argument rules that several entry points share, each worded with the entry's name (`who`).
+static int bf16_width_rule(int32_t d, const char* who) {
+  if (d <= 0 || (d % 8 == 0 && d <= 1024)) return HGNN_OK;   // (d <= 0: run_gather's bad sizes)
+  return fail(HGNN_E_UNSUPPORTED, "%s: d=%d (bf16 rows need d %% 8 == 0 and d <= 1024)", who, d);
+}
+static int acc_limit_rule(int64_t acc_limit, const char* who, int job = -1) {
+  if (acc_limit >= 0) return HGNN_OK;
+  if (job >= 0) return fail(HGNN_E_ARG, "%s: acc_limit[%d] < 0", who, job);
+  return fail(HGNN_E_ARG, "%s: acc_limit < 0", who);
+}
+static int row_w_rule(const float* row_w, int32_t flags, const char* who) {
+  if (!row_w || !(flags & HGNN_MEAN)) return HGNN_OK;
+  return fail(HGNN_E_ARG, "%s: row_w replaces HGNN_MEAN, not both", who);
+}
+
+// `n_x`: rows of the source table (the cache policy of the launch, nt_policy)
+static int run_gather(GatherArgs a, int64_t n_x, hipStream_t stream) {
+  nt_policy(a, n_x, elem_bytes(a));
   if (a.d <= 0 || a.n_rows < 0 || a.n_heavy < 0 || a.chunk <= 0)
     return fail(HGNN_E_ARG, "gather: bad sizes d=%d n_rows=%lld chunk=%d", a.d,
                 (long long)a.n_rows, a.chunk);
@@ -619,8 +643,17 @@ static int run_gather(GatherArgs a, hipStream_t stream) {
     return fail(HGNN_E_ARG, "score_gather: bad mode/arguments");
   if (a.rowptr2 && a.score != 1)
     return fail(HGNN_E_ARG, "score_gather2: needs mode 1 for the first list");
-  if (int rc = a.bf16 ? dispatch_gather_bf16(a, has_w, stream) : dispatch_gather(a, has_w, stream))
-    return rc;
+  const Variant v = a.score ? Variant::kScore
+                    : a.hot ? (has_w ? Variant::kHotWeighted : Variant::kHot)
+                            : (has_w ? Variant::kWeighted : Variant::kPlain);
+  int rc;
+  if (a.zp)
+    rc = launch_gather_zp(a, stream);
+  else if (a.bf16)
+    rc = with_shape_bf16(a.d, [&](auto s) { return launch_gather<uint16_t>(s, a, v, stream); });
+  else
+    rc = with_shape_f32(a.d, [&](auto s) { return launch_gather<float>(s, a, v, stream); });
+  if (rc) return rc;
   if (a.n_heavy > 0) {
     const dim3 grid((unsigned)a.n_heavy), block(256);
     if (a.d % 4 == 0) hipLaunchKernelGGL(k_fixup<4>, grid, block, 0, stream, a);
@@ -628,6 +661,28 @@ static int run_gather(GatherArgs a, hipStream_t stream) {
     return check_launch("k_fixup");
   }
   return HGNN_OK;
+}
+
+// The two-list score gathers: mode 1 over (rowptr, col) with the heavy-row plan, the negatives
+// (rowptr_n, col_n) in mode 2, one write per row; x holds fp32, bf16 or zero-packed fp32 rows.
+enum class Rows { kF32, kBf16, kZp };
+static int run_score2(const char* who, Rows rows, const void* x, int64_t n_x, const void* rowvec,
+                      int32_t d, const int32_t* rowptr, const int32_t* col,
+                      const int32_t* rowptr_n, const int32_t* col_n, int64_t n_rows,
+                      const float* cscale, float inv_e, const int32_t* heavy_rows,
+                      const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks, int32_t chunk,
+                      float* slab, float* out, hgnn_stream_t stream) {
+  if (rows == Rows::kBf16)
+    if (int rc = bf16_width_rule(d, who)) return rc;
+  if (rows == Rows::kZp && !zpack::width_ok(d))
+    return fail(HGNN_E_UNSUPPORTED, "%s: d=%d (zero-packed rows: 64 or 128)", who, d);
+  if (!rowptr_n && n_rows > 0) return fail(HGNN_E_ARG, "%s: rowptr_n is null", who);
+  GatherArgs a = gather_args(x, d, rowptr, col, n_rows, nullptr, nullptr, nullptr, 0, 0,
+                             heavy_rows, heavy_first, n_heavy, n_chunks, chunk, slab, out);
+  score_args(a, rowvec, cscale, inv_e, 1, rowptr_n, col_n);
+  a.bf16 = rows == Rows::kBf16;
+  a.zp = rows == Rows::kZp;
+  return run_gather(a, n_x, as_stream(stream));
 }
 
 }  // namespace hgnn
@@ -641,14 +696,9 @@ int hgnn_gather_reduce(const float* x, int64_t n_x, int32_t d, const int32_t* ro
                        const float* col_w, int32_t flags, const int32_t* heavy_rows,
                        const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
                        int32_t chunk, float* slab, float* out, hgnn_stream_t stream) {
-  GatherArgs a{};
-  a.x = x; a.rowptr = rowptr; a.col = col; a.edge_w = edge_w; a.col_w = col_w;
-  a.heavy_rows = heavy_rows; a.heavy_first = heavy_first; a.slab = slab; a.out = out;
-  a.n_rows = n_rows; a.n_heavy = n_heavy; a.n_items = n_rows + (n_heavy > 0 ? n_chunks : 0);
-  a.d = d; a.chunk = chunk; a.mean = (flags & HGNN_MEAN) ? 1 : 0;
-  a.accumulate = (flags & HGNN_ACCUMULATE) ? 1 : 0;
-  nt_policy(a, n_x);
-  return run_gather(a, as_stream(stream));
+  return run_gather(gather_args(x, d, rowptr, col, n_rows, edge_w, col_w, nullptr, flags, 0,
+                                heavy_rows, heavy_first, n_heavy, n_chunks, chunk, slab, out),
+                    n_x, as_stream(stream));
 }
 
 int32_t hgnn_hot_rows_policy(int64_t table_bytes, int32_t has_col_hot, float hot_share) {
@@ -661,20 +711,11 @@ int hgnn_gather_reduce_hot(const float* x, int64_t n_x, int32_t d, const int32_t
                            const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
                            int32_t chunk, float* slab, float* out, int64_t acc_limit,
                            const int32_t* col_hot, float hot_share, hgnn_stream_t stream) {
-  if (acc_limit < 0) return fail(HGNN_E_ARG, "gather_reduce_hot: acc_limit < 0");
-  GatherArgs a{};
-  a.x = x; a.rowptr = rowptr; a.col = col; a.edge_w = edge_w; a.col_w = col_w;
-  a.heavy_rows = heavy_rows; a.heavy_first = heavy_first; a.slab = slab; a.out = out;
-  a.n_rows = n_rows; a.n_heavy = n_heavy; a.n_items = n_rows + (n_heavy > 0 ? n_chunks : 0);
-  a.d = d; a.chunk = chunk; a.mean = (flags & HGNN_MEAN) ? 1 : 0;
-  a.accumulate = (flags & HGNN_ACCUMULATE) ? 1 : 0;
-  a.acc_limit = acc_limit;
-  nt_policy(a, n_x);
-  if (hot_policy(n_x * (int64_t)d * 4, col_hot != nullptr, hot_share)) {
-    a.col = col_hot;
-    a.hot = 1;
-  }
-  return run_gather(a, as_stream(stream));
+  if (int rc = acc_limit_rule(acc_limit, "gather_reduce_hot")) return rc;
+  GatherArgs a = gather_args(x, d, rowptr, col, n_rows, edge_w, col_w, nullptr, flags, acc_limit,
+                             heavy_rows, heavy_first, n_heavy, n_chunks, chunk, slab, out);
+  hot_args(a, n_x, col_hot, hot_share);
+  return run_gather(a, n_x, as_stream(stream));
 }
 
 int hgnn_gather_reduce_multi(int32_t n_jobs, const float* const* x, const int64_t* n_x, int32_t d,
@@ -689,39 +730,39 @@ int hgnn_gather_reduce_multi(int32_t n_jobs, const float* const* x, const int64_
   m.n = n_jobs;
   bool has_w = false;
   for (int j = 0; j < n_jobs; ++j) {
-    GatherArgs& a = m.j[j];
     if (n_rows[j] < 0 || (n_rows[j] > 0 && (!rowptr[j] || !out[j])))
       return fail(HGNN_E_ARG, "gather_reduce_multi: job %d: null rowptr/out", j);
     for (int i = 0; i < j; ++i)
       if (n_rows[j] > 0 && out[i] == out[j])
         return fail(HGNN_E_ARG, "gather_reduce_multi: jobs %d and %d share an output", i, j);
-    a.x = x[j]; a.rowptr = rowptr[j]; a.col = col[j]; a.out = out[j];
-    a.edge_w = edge_w ? edge_w[j] : nullptr;
-    has_w |= a.edge_w != nullptr;
-    a.n_rows = n_rows[j]; a.n_items = n_rows[j]; a.d = d; a.chunk = INT32_MAX;
-    a.mean = (flags & HGNN_MEAN) ? 1 : 0;
-    a.accumulate = (flags & HGNN_ACCUMULATE) ? 1 : 0;
-    a.acc_limit = acc_limit ? acc_limit[j] : 0;
-    if (a.acc_limit < 0) return fail(HGNN_E_ARG, "gather_reduce_multi: acc_limit[%d] < 0", j);
-    nt_policy(a, n_x[j]);
+    const int64_t limit = acc_limit ? acc_limit[j] : 0;
+    if (int rc = acc_limit_rule(limit, "gather_reduce_multi", j)) return rc;
+    // light rows only: no heavy-row plan, no row is ever split
+    m.j[j] = gather_args(x[j], d, rowptr[j], col[j], n_rows[j], edge_w ? edge_w[j] : nullptr,
+                         nullptr, nullptr, flags, limit, nullptr, nullptr, 0, 0, INT32_MAX,
+                         nullptr, out[j]);
+    has_w |= m.j[j].edge_w != nullptr;
+    nt_policy(m.j[j], n_x[j]);
     m.base[j + 1] = m.base[j] + n_rows[j];
   }
   if (m.base[n_jobs] == 0) return HGNN_OK;
   const dim3 grid((unsigned)cdiv(m.base[n_jobs], 4)), block(256);
   hipStream_t stream = as_stream(stream_);
-  // the row widths dispatch_gather takes at d % 4 == 0 (d = 64: its mean / weighted depths)
-  const int nv = d / 4;
-#define HGNN_GM(LPR, VPL, U, UW)                                                                 \
-  if (has_w) hipLaunchKernelGGL((k_gather_multi<LPR, VPL, 4, UW, true>), grid, block, 0, stream, m); \
-  else hipLaunchKernelGGL((k_gather_multi<LPR, VPL, 4, U, false>), grid, block, 0, stream, m);
-  if (nv <= 4) { HGNN_GM(4, 1, 4, 4) }
-  else if (nv <= 8) { HGNN_GM(8, 1, 4, 4) }
-  else if (nv <= 16) { HGNN_GM(16, 1, 8, 6) }
-  else if (nv <= 32) { HGNN_GM(32, 1, 4, 4) }
-  else if (nv <= 64) { HGNN_GM(64, 1, 4, 4) }
-  else { HGNN_GM(64, 2, 2, 2) }
-#undef HGNN_GM
-  return check_launch("k_gather_multi");
+  // the rows of the fp32 table that the d rule above admits: float4 rows up to d = 512
+  return with_shape_f32(d, [&](auto s) {
+    using S = decltype(s);
+    if constexpr (S::W == 4 && S::LPR * S::VPL * S::W <= 512) {
+      if (has_w)
+        hipLaunchKernelGGL((k_gather_multi<S::LPR, S::VPL, 4, S::UW, true>), grid, block, 0,
+                           stream, m);
+      else
+        hipLaunchKernelGGL((k_gather_multi<S::LPR, S::VPL, 4, S::UM, false>), grid, block, 0,
+                           stream, m);
+      return check_launch("k_gather_multi");
+    } else {
+      return fail(HGNN_E_ARG, "gather_reduce_multi: no launch at d=%d", d);
+    }
+  });
 }
 
 int hgnn_gather_reduce_scaled(const float* x, int64_t n_x, int32_t d, const int32_t* rowptr,
@@ -730,16 +771,12 @@ int hgnn_gather_reduce_scaled(const float* x, int64_t n_x, int32_t d, const int3
                               const int32_t* heavy_rows, const int32_t* heavy_first,
                               int64_t n_heavy, int64_t n_chunks, int32_t chunk, float* slab,
                               float* out, hgnn_stream_t stream) {
-  if (row_w && (flags & HGNN_MEAN))
-    return fail(HGNN_E_ARG, "gather_reduce_scaled: row_w replaces HGNN_MEAN, not both");
-  GatherArgs a{};
-  a.x = x; a.rowptr = rowptr; a.col = col; a.edge_w = edge_w; a.col_w = col_w; a.row_w = row_w;
-  a.heavy_rows = heavy_rows; a.heavy_first = heavy_first; a.slab = slab; a.out = out;
-  a.n_rows = n_rows; a.n_heavy = n_heavy; a.n_items = n_rows + (n_heavy > 0 ? n_chunks : 0);
-  a.d = d; a.chunk = chunk; a.mean = 0;
-  a.accumulate = (flags & HGNN_ACCUMULATE) ? 1 : 0;
-  nt_policy(a, n_x);
-  return run_gather(a, as_stream(stream));
+  if (int rc = row_w_rule(row_w, flags, "gather_reduce_scaled")) return rc;
+  // (HGNN_MEAN is not read here: the scale is row_w, or 1 without one)
+  return run_gather(gather_args(x, d, rowptr, col, n_rows, edge_w, col_w, row_w,
+                                flags & ~HGNN_MEAN, 0, heavy_rows, heavy_first, n_heavy, n_chunks,
+                                chunk, slab, out),
+                    n_x, as_stream(stream));
 }
 
 int hgnn_gather_reduce_bf16(const uint16_t* x, int64_t n_x, int32_t d, const int32_t* rowptr,
@@ -749,35 +786,23 @@ int hgnn_gather_reduce_bf16(const uint16_t* x, int64_t n_x, int32_t d, const int
                             int64_t n_heavy, int64_t n_chunks, int32_t chunk, float* slab,
                             float* out, int64_t acc_limit, const int32_t* col_hot,
                             float hot_share, hgnn_stream_t stream) {
-  if (d > 0 && (d % 8 != 0 || d > 1024))
-    return fail(HGNN_E_UNSUPPORTED,
-                "gather_reduce_bf16: d=%d (bf16 rows need d %% 8 == 0 and d <= 1024)", d);
-  if (row_w && (flags & HGNN_MEAN))
-    return fail(HGNN_E_ARG, "gather_reduce_bf16: row_w replaces HGNN_MEAN, not both");
-  if (acc_limit < 0) return fail(HGNN_E_ARG, "gather_reduce_bf16: acc_limit < 0");
-  GatherArgs a{};
-  a.x = x; a.rowptr = rowptr; a.col = col; a.edge_w = edge_w; a.col_w = col_w; a.row_w = row_w;
-  a.heavy_rows = heavy_rows; a.heavy_first = heavy_first; a.slab = slab; a.out = out;
-  a.n_rows = n_rows; a.n_heavy = n_heavy; a.n_items = n_rows + (n_heavy > 0 ? n_chunks : 0);
-  a.d = d; a.chunk = chunk; a.mean = (flags & HGNN_MEAN) ? 1 : 0;
-  a.accumulate = (flags & HGNN_ACCUMULATE) ? 1 : 0;
-  a.acc_limit = acc_limit;
+  if (int rc = bf16_width_rule(d, "gather_reduce_bf16")) return rc;
+  if (int rc = row_w_rule(row_w, flags, "gather_reduce_bf16")) return rc;
+  if (int rc = acc_limit_rule(acc_limit, "gather_reduce_bf16")) return rc;
+  GatherArgs a = gather_args(x, d, rowptr, col, n_rows, edge_w, col_w, row_w, flags, acc_limit,
+                             heavy_rows, heavy_first, n_heavy, n_chunks, chunk, slab, out);
   a.bf16 = 1;
-  nt_policy(a, n_x, 2);
-  if (hot_policy(n_x * (int64_t)d * 2, col_hot != nullptr, hot_share)) {
-    a.col = col_hot;
-    a.hot = 1;
-  }
-  return run_gather(a, as_stream(stream));
+  hot_args(a, n_x, col_hot, hot_share);
+  return run_gather(a, n_x, as_stream(stream));
 }
 
 int hgnn_gather_mean_fwd(const float* x_src, int64_t n_src, int32_t d, const int32_t* rowptr,
                          const int32_t* col, int64_t n_dst, const int32_t* heavy_rows,
                          const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
                          int32_t chunk, float* slab, float* aggr, hgnn_stream_t stream) {
-  return hgnn_gather_reduce(x_src, n_src, d, rowptr, col, n_dst, nullptr, nullptr, HGNN_MEAN,
-                            heavy_rows, heavy_first, n_heavy, n_chunks, chunk, slab, aggr,
-                            stream);
+  return run_gather(gather_args(x_src, d, rowptr, col, n_dst, nullptr, nullptr, nullptr, HGNN_MEAN,
+                                0, heavy_rows, heavy_first, n_heavy, n_chunks, chunk, slab, aggr),
+                    n_src, as_stream(stream));
 }
 
 int hgnn_scatter_mean_bwd(const float* grad_aggr, int64_t n_dst, const float* inv_deg,
@@ -786,9 +811,10 @@ int hgnn_scatter_mean_bwd(const float* grad_aggr, int64_t n_dst, const float* in
                           int64_t n_heavy, int64_t n_chunks, int32_t chunk, float* slab,
                           float* grad_x_src, int32_t accumulate, hgnn_stream_t stream) {
   if (!inv_deg && n_src > 0) return fail(HGNN_E_ARG, "scatter_mean_bwd: inv_deg is null");
-  return hgnn_gather_reduce(grad_aggr, n_dst, d, t_rowptr, t_col, n_src, nullptr, inv_deg,
-                            accumulate ? HGNN_ACCUMULATE : 0, heavy_rows, heavy_first, n_heavy,
-                            n_chunks, chunk, slab, grad_x_src, stream);
+  return run_gather(gather_args(grad_aggr, d, t_rowptr, t_col, n_src, nullptr, inv_deg, nullptr,
+                                accumulate ? HGNN_ACCUMULATE : 0, 0, heavy_rows, heavy_first,
+                                n_heavy, n_chunks, chunk, slab, grad_x_src),
+                    n_dst, as_stream(stream));
 }
 
 int hgnn_score_gather(const float* x, int64_t n_x, const float* rowvec, int32_t d,
@@ -798,14 +824,11 @@ int hgnn_score_gather(const float* x, int64_t n_x, const float* rowvec, int32_t 
                       int32_t chunk, float* slab, float* out, int32_t accumulate,
                       hgnn_stream_t stream) {
   if (mode != 1 && mode != 2) return fail(HGNN_E_ARG, "score_gather: mode=%d", mode);
-  GatherArgs a{};
-  a.x = x; a.rowptr = rowptr; a.col = col;
-  a.heavy_rows = heavy_rows; a.heavy_first = heavy_first; a.slab = slab; a.out = out;
-  a.n_rows = n_rows; a.n_heavy = n_heavy; a.n_items = n_rows + (n_heavy > 0 ? n_chunks : 0);
-  a.d = d; a.chunk = chunk; a.accumulate = accumulate ? 1 : 0;
-  a.rowvec = rowvec; a.cscale = cscale; a.inv_e = inv_e; a.score = mode;
-  nt_policy(a, n_x);
-  return run_gather(a, as_stream(stream));
+  GatherArgs a = gather_args(x, d, rowptr, col, n_rows, nullptr, nullptr, nullptr,
+                             accumulate ? HGNN_ACCUMULATE : 0, 0, heavy_rows, heavy_first, n_heavy,
+                             n_chunks, chunk, slab, out);
+  score_args(a, rowvec, cscale, inv_e, mode);
+  return run_gather(a, n_x, as_stream(stream));
 }
 
 int hgnn_score_gather2(const float* x, int64_t n_x, const float* rowvec, int32_t d,
@@ -814,16 +837,9 @@ int hgnn_score_gather2(const float* x, int64_t n_x, const float* rowvec, int32_t
                        const int32_t* heavy_rows, const int32_t* heavy_first, int64_t n_heavy,
                        int64_t n_chunks, int32_t chunk, float* slab, float* out,
                        hgnn_stream_t stream) {
-  if (!rowptr_n && n_rows > 0) return fail(HGNN_E_ARG, "score_gather2: rowptr_n is null");
-  GatherArgs a{};
-  a.x = x; a.rowptr = rowptr; a.col = col;
-  a.heavy_rows = heavy_rows; a.heavy_first = heavy_first; a.slab = slab; a.out = out;
-  a.n_rows = n_rows; a.n_heavy = n_heavy; a.n_items = n_rows + (n_heavy > 0 ? n_chunks : 0);
-  a.d = d; a.chunk = chunk;
-  a.rowvec = rowvec; a.cscale = cscale; a.inv_e = inv_e; a.score = 1;
-  a.rowptr2 = rowptr_n; a.col2 = col_n;
-  nt_policy(a, n_x);
-  return run_gather(a, as_stream(stream));
+  return run_score2("score_gather2", Rows::kF32, x, n_x, rowvec, d, rowptr, col, rowptr_n, col_n,
+                    n_rows, cscale, inv_e, heavy_rows, heavy_first, n_heavy, n_chunks, chunk, slab,
+                    out, stream);
 }
 
 int hgnn_score_gather2_zp(const void* xz, int64_t n_x, const float* rowvec, int32_t d,
@@ -832,19 +848,9 @@ int hgnn_score_gather2_zp(const void* xz, int64_t n_x, const float* rowvec, int3
                           const int32_t* heavy_rows, const int32_t* heavy_first, int64_t n_heavy,
                           int64_t n_chunks, int32_t chunk, float* slab, float* out,
                           hgnn_stream_t stream) {
-  if (!zpack::width_ok(d))
-    return fail(HGNN_E_UNSUPPORTED, "score_gather2_zp: d=%d (zero-packed rows: 64 or 128)", d);
-  if (!rowptr_n && n_rows > 0) return fail(HGNN_E_ARG, "score_gather2_zp: rowptr_n is null");
-  GatherArgs a{};
-  a.x = xz; a.rowptr = rowptr; a.col = col;
-  a.heavy_rows = heavy_rows; a.heavy_first = heavy_first; a.slab = slab; a.out = out;
-  a.n_rows = n_rows; a.n_heavy = n_heavy; a.n_items = n_rows + (n_heavy > 0 ? n_chunks : 0);
-  a.d = d; a.chunk = chunk;
-  a.rowvec = rowvec; a.cscale = cscale; a.inv_e = inv_e; a.score = 1;
-  a.rowptr2 = rowptr_n; a.col2 = col_n;
-  a.zp = 1;
-  nt_policy(a, n_x);   // by the size of the unpacked table: the policy of hgnn_score_gather2
-  return run_gather(a, as_stream(stream));
+  return run_score2("score_gather2_zp", Rows::kZp, xz, n_x, rowvec, d, rowptr, col, rowptr_n, col_n,
+                    n_rows, cscale, inv_e, heavy_rows, heavy_first, n_heavy, n_chunks, chunk, slab,
+                    out, stream);
 }
 
 int hgnn_score_gather2_bf16(const uint16_t* x, int64_t n_x, const uint16_t* rowvec, int32_t d,
@@ -853,20 +859,9 @@ int hgnn_score_gather2_bf16(const uint16_t* x, int64_t n_x, const uint16_t* rowv
                             float inv_e, const int32_t* heavy_rows, const int32_t* heavy_first,
                             int64_t n_heavy, int64_t n_chunks, int32_t chunk, float* slab,
                             float* out, hgnn_stream_t stream) {
-  if (d > 0 && (d % 8 != 0 || d > 1024))
-    return fail(HGNN_E_UNSUPPORTED,
-                "score_gather2_bf16: d=%d (bf16 rows need d %% 8 == 0 and d <= 1024)", d);
-  if (!rowptr_n && n_rows > 0) return fail(HGNN_E_ARG, "score_gather2_bf16: rowptr_n is null");
-  GatherArgs a{};
-  a.x = x; a.rowptr = rowptr; a.col = col;
-  a.heavy_rows = heavy_rows; a.heavy_first = heavy_first; a.slab = slab; a.out = out;
-  a.n_rows = n_rows; a.n_heavy = n_heavy; a.n_items = n_rows + (n_heavy > 0 ? n_chunks : 0);
-  a.d = d; a.chunk = chunk;
-  a.rowvec = rowvec; a.cscale = cscale; a.inv_e = inv_e; a.score = 1;
-  a.rowptr2 = rowptr_n; a.col2 = col_n;
-  a.bf16 = 1;
-  nt_policy(a, n_x, 2);
-  return run_gather(a, as_stream(stream));
+  return run_score2("score_gather2_bf16", Rows::kBf16, x, n_x, rowvec, d, rowptr, col, rowptr_n,
+                    col_n, n_rows, cscale, inv_e, heavy_rows, heavy_first, n_heavy, n_chunks, chunk,
+                    slab, out, stream);
 }
 
 }  // extern "C"

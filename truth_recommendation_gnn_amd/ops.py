@@ -179,29 +179,52 @@ def gather_blocks(x: torch.Tensor, n_edges: Optional[int] = None) -> int:
     return int(-(-nbytes // GATHER_BLOCK_SLICE))
 
 
+class _PlanArgs(tuple):
+    """``_plan_args``' result; it also holds the slab: keep it until the launch is enqueued."""
+
+
+def _plan_args(p, d: int, dev) -> _PlanArgs:
+    """``(heavy_rows, heavy_first, n_heavy, n_chunks, chunk, slab)`` in ABI order for a gather of
+    ``d`` columns; the slab (the heavy rows' partial sums) is allocated when there are any."""
+    slab = torch.empty(p.n_chunks * d, dtype=torch.float32, device=dev) if p.n_heavy else None
+    args = _PlanArgs((N.ptr(p.heavy_rows), N.ptr(p.heavy_first), p.n_heavy, p.n_chunks, p.chunk,
+                      N.ptr(slab)))
+    args.slab = slab
+    return args
+
+
+def _launch_gather(x, g, edge_w, col_w, row_w, flags, out, hot=None):
+    """One K1 / K2 launch over grouping ``g`` through the entry point that the table's dtype,
+    ``hot`` (the grouping's ``graph.HotCols``: two-policy row loads, same sums) and ``row_w`` (a
+    per-row scale in place of the mean) select."""
+    d = int(out.shape[1])
+    dev = out.device
+    lib, s = N.lib(), N.stream_ptr(dev)
+    plan = _plan_args(g.plan, d, dev)
+    head = (N.ptr(x), x.shape[0], d, N.ptr(g.rowptr), N.ptr(g.col), g.n_rows, N.ptr(edge_w),
+            N.ptr(col_w))
+    if x.dtype == torch.bfloat16:
+        N.check(lib.hgnn_gather_reduce_bf16(
+            *head, N.ptr(row_w), flags, *plan, N.ptr(out), 0,
+            N.ptr(hot.col) if hot is not None else None, hot.share if hot is not None else 0.0,
+            s), "hgnn_gather_reduce_bf16")
+    elif row_w is not None:     # (the source-blocked passes: no caller has hot columns for them)
+        N.check(lib.hgnn_gather_reduce_scaled(*head, N.ptr(row_w), flags, *plan, N.ptr(out), s),
+                "hgnn_gather_reduce_scaled")
+    elif hot is not None:
+        N.check(lib.hgnn_gather_reduce_hot(*head, flags, *plan, N.ptr(out), 0, N.ptr(hot.col),
+                                           hot.share, s), "hgnn_gather_reduce_hot")
+    else:
+        N.check(lib.hgnn_gather_reduce(*head, flags, *plan, N.ptr(out), s), "hgnn_gather_reduce")
+
+
 def _gather_blocked(x, passes, row_w, edge_w, out, accumulate, name, nbytes, cbytes):
     """All passes of a source-blocked gather, timed as one gather (its algorithmic bytes are the
     unblocked gather's)."""
-    dev = out.device
-    d = int(out.shape[1])
-    lib, s = N.lib(), N.stream_ptr(dev)
     with _timed(name, nbytes, cbytes):
         for b, g in enumerate(passes):
-            p = g.plan
-            slab = (torch.empty(p.n_chunks * d, dtype=torch.float32, device=dev)
-                    if p.n_heavy else None)
             flags = N.HGNN_ACCUMULATE if (accumulate or b > 0) else 0
-            if x.dtype == torch.bfloat16:
-                N.check(lib.hgnn_gather_reduce_bf16(
-                    N.ptr(x), x.shape[0], d, N.ptr(g.rowptr), N.ptr(g.col), g.n_rows,
-                    N.ptr(edge_w), None, N.ptr(row_w), flags, N.ptr(p.heavy_rows),
-                    N.ptr(p.heavy_first), p.n_heavy, p.n_chunks, p.chunk, N.ptr(slab), N.ptr(out),
-                    0, None, 0.0, s), "hgnn_gather_reduce_bf16")
-                continue
-            N.check(lib.hgnn_gather_reduce_scaled(
-                N.ptr(x), x.shape[0], d, N.ptr(g.rowptr), N.ptr(g.col), g.n_rows, N.ptr(edge_w),
-                None, N.ptr(row_w), flags, N.ptr(p.heavy_rows), N.ptr(p.heavy_first), p.n_heavy,
-                p.n_chunks, p.chunk, N.ptr(slab), N.ptr(out), s), "hgnn_gather_reduce_scaled")
+            _launch_gather(x, g, edge_w, None, row_w, flags, out)
 
 
 # ----------------------------------------------------------------------------- static aggregates
@@ -488,11 +511,6 @@ def _table_bytes(x: torch.Tensor) -> int:
 def _gather(x, grouped, col_w, csr_mean, out, accumulate, edge_w=None, kind=None, hot=None):
     """``hot``: the grouping's ``graph.HotCols`` (``RelationCSR.hot_cols``) or None; with one the
     launch goes through ``hgnn_gather_reduce_hot`` (two-policy row loads, same sums)."""
-    p = grouped.plan
-    dev = out.device
-    slab = None
-    if p.n_heavy:
-        slab = torch.empty(p.n_chunks * out.shape[1], dtype=torch.float32, device=dev)
     flags = (N.HGNN_MEAN if csr_mean else 0) | (N.HGNN_ACCUMULATE if accumulate else 0)
     d = int(out.shape[1])
     weighted = edge_w is not None or col_w is not None
@@ -502,38 +520,15 @@ def _gather(x, grouped, col_w, csr_mean, out, accumulate, edge_w=None, kind=None
     rb = _row_bytes(x)
     with _timed(name, gather_bytes(E, grouped.n_rows, d, weighted, rb),
                 gather_compulsory_bytes(E, grouped.n_rows, int(x.shape[0]), d, weighted, rb)):
-        if x.dtype == torch.bfloat16:
-            N.check(N.lib().hgnn_gather_reduce_bf16(
-                N.ptr(x), x.shape[0], d, N.ptr(grouped.rowptr), N.ptr(grouped.col),
-                grouped.n_rows, N.ptr(edge_w), N.ptr(col_w), None, flags, N.ptr(p.heavy_rows),
-                N.ptr(p.heavy_first), p.n_heavy, p.n_chunks, p.chunk, N.ptr(slab), N.ptr(out),
-                0, N.ptr(hot.col) if hot is not None else None,
-                hot.share if hot is not None else 0.0, N.stream_ptr(dev)),
-                "hgnn_gather_reduce_bf16")
-            return
-        if hot is not None:
-            N.check(N.lib().hgnn_gather_reduce_hot(
-                N.ptr(x), x.shape[0], d, N.ptr(grouped.rowptr), N.ptr(grouped.col),
-                grouped.n_rows, N.ptr(edge_w), N.ptr(col_w), flags, N.ptr(p.heavy_rows),
-                N.ptr(p.heavy_first), p.n_heavy, p.n_chunks, p.chunk, N.ptr(slab), N.ptr(out),
-                0, N.ptr(hot.col), hot.share, N.stream_ptr(dev)), "hgnn_gather_reduce_hot")
-            return
-        N.check(N.lib().hgnn_gather_reduce(
-            N.ptr(x), x.shape[0], d, N.ptr(grouped.rowptr), N.ptr(grouped.col),
-            grouped.n_rows, N.ptr(edge_w), N.ptr(col_w), flags, N.ptr(p.heavy_rows),
-            N.ptr(p.heavy_first), p.n_heavy, p.n_chunks, p.chunk, N.ptr(slab), N.ptr(out),
-            N.stream_ptr(dev)), "hgnn_gather_reduce")
+        _launch_gather(x, grouped, edge_w, col_w, None, flags, out, hot)
 
 
 def _score_gather(U, P, grouped, mode, cscale, inv_e, out, accumulate, tag):
     """dP rows from the loss: each edge's weight recomputed from <U[u], P[row]> (mode 1 positive,
     2 negative) inside the gather — see hgnn_score_gather."""
-    p = grouped.plan
     dev = out.device
     d = int(out.shape[1])
-    slab = None
-    if p.n_heavy:
-        slab = torch.empty(p.n_chunks * d, dtype=torch.float32, device=dev)
+    plan = _plan_args(grouped.plan, d, dev)
     E = int(grouped.col.numel())
     nb = gather_bytes(E, grouped.n_rows, d, False) + 4 * grouped.n_rows * d
     cb = (gather_compulsory_bytes(E, grouped.n_rows, int(U.shape[0]), d, False)
@@ -541,9 +536,8 @@ def _score_gather(U, P, grouped, mode, cscale, inv_e, out, accumulate, tag):
     with _timed(f"score_gather_{tag}[{grouped.n_rows}<-{U.shape[0]}]x{d}", nb, cb):
         N.check(N.lib().hgnn_score_gather(
             N.ptr(U), U.shape[0], N.ptr(P), d, N.ptr(grouped.rowptr), N.ptr(grouped.col),
-            grouped.n_rows, mode, N.ptr(cscale), inv_e, N.ptr(p.heavy_rows), N.ptr(p.heavy_first),
-            p.n_heavy, p.n_chunks, p.chunk, N.ptr(slab), N.ptr(out), 1 if accumulate else 0,
-            N.stream_ptr(dev)), "hgnn_score_gather")
+            grouped.n_rows, mode, N.ptr(cscale), inv_e, *plan, N.ptr(out),
+            1 if accumulate else 0, N.stream_ptr(dev)), "hgnn_score_gather")
 
 
 def _score_gather2(U, P, pos, negs, cscale, inv_e, out, Uz=None):
@@ -551,37 +545,22 @@ def _score_gather2(U, P, pos, negs, cscale, inv_e, out, Uz=None):
     heavy-row plan) and its negatives (mode 2) into one accumulator and writes dP[r] once.
     ``Uz``: ``zpack_rows(U)``; the gather then reads the packed rows (same sums, bit for bit;
     the timer entry keeps its name and the unpacked table's algorithmic bytes)."""
-    p = pos.plan
     dev = out.device
     d = int(out.shape[1])
     n = pos.n_rows
-    slab = None
-    if p.n_heavy:
-        slab = torch.empty(p.n_chunks * d, dtype=torch.float32, device=dev)
+    plan = _plan_args(pos.plan, d, dev)
     E = int(pos.col.numel()) + int(negs.col.numel())
     rb = _row_bytes(U)      # U's rows per edge and P's own row per output row
     nb = gather_bytes(E, n, d, False, rb) + 4 * (n + 1) + n * rb
     cb = gather_compulsory_bytes(E, n, int(U.shape[0]), d, False, rb) + 4 * (n + 1) + n * rb
+    # the entry point by the rows it reads: bf16, zero-packed fp32, fp32
+    entry, table = (("hgnn_score_gather2_bf16", U) if U.dtype == torch.bfloat16 else
+                    ("hgnn_score_gather2_zp", Uz) if Uz is not None else ("hgnn_score_gather2", U))
     with _timed(f"score_gather[{n}<-{U.shape[0]}]x{d}", nb, cb):
-        if U.dtype == torch.bfloat16:
-            N.check(N.lib().hgnn_score_gather2_bf16(
-                N.ptr(U), U.shape[0], N.ptr(P), d, N.ptr(pos.rowptr), N.ptr(pos.col),
-                N.ptr(negs.rowptr), N.ptr(negs.col), n, N.ptr(cscale), inv_e,
-                N.ptr(p.heavy_rows), N.ptr(p.heavy_first), p.n_heavy, p.n_chunks, p.chunk,
-                N.ptr(slab), N.ptr(out), N.stream_ptr(dev)), "hgnn_score_gather2_bf16")
-            return
-        if Uz is not None:
-            N.check(N.lib().hgnn_score_gather2_zp(
-                N.ptr(Uz), U.shape[0], N.ptr(P), d, N.ptr(pos.rowptr), N.ptr(pos.col),
-                N.ptr(negs.rowptr), N.ptr(negs.col), n, N.ptr(cscale), inv_e,
-                N.ptr(p.heavy_rows), N.ptr(p.heavy_first), p.n_heavy, p.n_chunks, p.chunk,
-                N.ptr(slab), N.ptr(out), N.stream_ptr(dev)), "hgnn_score_gather2_zp")
-            return
-        N.check(N.lib().hgnn_score_gather2(
-            N.ptr(U), U.shape[0], N.ptr(P), d, N.ptr(pos.rowptr), N.ptr(pos.col),
-            N.ptr(negs.rowptr), N.ptr(negs.col), n, N.ptr(cscale), inv_e, N.ptr(p.heavy_rows),
-            N.ptr(p.heavy_first), p.n_heavy, p.n_chunks, p.chunk, N.ptr(slab), N.ptr(out),
-            N.stream_ptr(dev)), "hgnn_score_gather2")
+        N.check(getattr(N.lib(), entry)(
+            N.ptr(table), U.shape[0], N.ptr(P), d, N.ptr(pos.rowptr), N.ptr(pos.col),
+            N.ptr(negs.rowptr), N.ptr(negs.col), n, N.ptr(cscale), inv_e, *plan, N.ptr(out),
+            N.stream_ptr(dev)), entry)
 
 
 def scatter_mean_bwd(grad_aggr: torch.Tensor, csr: RelationCSR,
@@ -1539,34 +1518,57 @@ def _row_range(grouped, lo: int, hi: int):
     return g
 
 
-def _sort_negatives(csr, neg_u_order, draw, neg, neg32: bool, uop, E: int, np_: int, err,
-                    dev):
+class _Negatives(NamedTuple):
+    """The loss's negatives in the user-grouped order, in exactly one of the three forms they
+    come in: an int64 tensor (``torch.randint``'s), an int32 tensor (``sample_negatives``': in
+    range by construction) or a ``NegativeDraw`` (drawn again wherever they are read: the sort's
+    first pass, the scoring pass)."""
+    i64: Optional[torch.Tensor]
+    i32: Optional[torch.Tensor]
+    draw: Optional["NegativeDraw"]
+
+    @classmethod
+    def of(cls, neg_u_order, E: int, n_posts: int) -> "_Negatives":
+        """``neg_u_order`` checked against the ``E`` positive edges and ``n_posts``."""
+        if isinstance(neg_u_order, NegativeDraw):
+            if neg_u_order.n != E or neg_u_order.num_posts != n_posts:
+                raise ValueError("edge_bce_loss: the NegativeDraw does not match the positive "
+                                 "edges")
+            return cls(None, None, neg_u_order)
+        if neg_u_order.numel() != E:
+            raise ValueError("edge_bce_loss: one negative per positive edge is required")
+        if neg_u_order.dtype == torch.int32:
+            return cls(None, neg_u_order.contiguous(), None)
+        return cls(neg_u_order.to(torch.int64).contiguous(), None, None)
+
+
+def _sort_negatives(negs: _Negatives, uop, E: int, np_: int, err, dev):
     """The negatives (user-grouped order) grouped by post: (rowptr over posts, users in that
     order), stable — the order the dP gather sums them in."""
     lib = N.lib()
     rowptr_n = torch.empty(np_ + 1, dtype=torch.int32, device=dev)
     nu_s = torch.empty(E, dtype=torch.int32, device=dev)
     ws = N.workspace(lib.hgnn_sort_pairs_ws_bytes(E, np_), dev)
-    if draw is not None:
+    if negs.draw is not None:
         # draws computed in the sort's first pass (and again in the scoring pass: no
         # position-order copy is written)
         with _timed("sort_negatives", 4 * E * (2 * 4)):
             N.check(lib.hgnn_draw_sort_negatives(
-                N.ptr(draw.seed), N.ptr(uop), E, np_, None, N.ptr(rowptr_n),
+                N.ptr(negs.draw.seed), N.ptr(uop), E, np_, None, N.ptr(rowptr_n),
                 N.ptr(nu_s), N.ptr(ws), ws.numel(), N.stream_ptr(dev)),
                 "hgnn_draw_sort_negatives")
-    elif neg32:
+    elif negs.i32 is not None:
         # int32 keys: no validation pass (the scoring pass below counts out-of-range
         # negatives; the sort only misplaces such a key, never dereferences it)
         with _timed("sort_negatives", 4 * E * (2 * 4) + 4 * E):
             N.check(lib.hgnn_sort_pairs_i32(
-                N.ptr(neg), N.ptr(uop), None, E, np_, N.ptr(rowptr_n), N.ptr(nu_s),
+                N.ptr(negs.i32), N.ptr(uop), None, E, np_, N.ptr(rowptr_n), N.ptr(nu_s),
                 None, None, N.ptr(ws), ws.numel(), N.stream_ptr(dev)),
                 "hgnn_sort_pairs_i32")
     else:
         with _timed("sort_negatives", 4 * E * (2 + 1 + 4) + 4 * E):
             N.check(lib.hgnn_sort_pairs_i64(
-                N.ptr(neg), N.ptr(uop), None, E, np_, N.ptr(rowptr_n), N.ptr(nu_s),
+                N.ptr(negs.i64), N.ptr(uop), None, E, np_, N.ptr(rowptr_n), N.ptr(nu_s),
                 None, N.ptr(err[1:]), N.ptr(ws), ws.numel(), N.stream_ptr(dev)),
                 "hgnn_sort_pairs_i64")
     return rowptr_n, nu_s
@@ -1596,16 +1598,6 @@ class PresortedNegatives:
             raise ValueError("edge_bce_loss: the presorted negatives are for other edges")
 
 
-def _neg_inputs(neg_u_order):
-    draw = neg_u_order if isinstance(neg_u_order, NegativeDraw) else None
-    neg32 = neg_u_order.dtype == torch.int32
-    if draw is not None:
-        neg = None
-    else:
-        neg = neg_u_order.contiguous() if neg32 else neg_u_order.to(torch.int64).contiguous()
-    return draw, neg32, neg
-
-
 def presort_negatives(n_users: int, n_posts: int, pos_edges: torch.Tensor, neg_p,
                       neg_order: str) -> PresortedNegatives:
     """The grouping ``edge_bce_loss_raw`` would sort its negatives into, done now (it needs
@@ -1613,13 +1605,11 @@ def presort_negatives(n_users: int, n_posts: int, pos_edges: torch.Tensor, neg_p
     same ``neg_p`` and ``neg_order`` (required here: the two loss entry points default to
     different orders)."""
     csr = relation_csr_for_loss(pos_edges, n_users, n_posts)
-    neg_u = _negatives_user_order(csr, neg_p, neg_order)
-    draw, neg32, neg = _neg_inputs(neg_u)
+    E = csr.num_edges
+    negs = _Negatives.of(_negatives_user_order(csr, neg_p, neg_order), E, n_posts)
     dev = csr.fwd.rowptr.device
     err = torch.zeros(2, dtype=torch.int32, device=dev)
-    E = csr.num_edges
-    rp, us = _sort_negatives(csr, neg_u, draw, neg, neg32, _user_of_pos(csr), E, n_posts, err,
-                             dev)
+    rp, us = _sort_negatives(negs, _user_of_pos(csr), E, n_posts, err, dev)
     return PresortedNegatives(csr, neg_p, neg_order, n_posts, rp, us)
 
 
@@ -1637,24 +1627,10 @@ def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total:
     then read the bf16 rows, so the score <R(U[u]), R(P[p])> is one number in the scoring pass
     and in the dP gather; loss, dU and dP stay fp32).  The sharded step's arguments (``ready``,
     ``on_dP``, ``p_chunks``) are for fp32 rows only."""
-    bf16 = U.dtype == torch.bfloat16
-    relu_out = bool(getattr(U, RELU_OUT, False))   # (read here: .contiguous() may copy)
-    if bf16:
-        if P.dtype != torch.bfloat16:
-            raise TypeError("edge_bce_loss: bf16 rows need both tables in bfloat16")
-        if ready is not None or on_dP is not None or p_chunks is not None:
-            raise ValueError("edge_bce_loss: bf16 rows do not combine with ready / on_dP / "
-                             "p_chunks (the sharded step runs on fp32 rows)")
-        U, P = U.contiguous(), P.contiguous()
-    else:
-        U = _check_f32(U, "edge_bce_loss user_emb")
-        P = _check_f32(P, "edge_bce_loss post_emb")
-    draw = neg_u_order if isinstance(neg_u_order, NegativeDraw) else None
-    dev = N.require_device(U, P, draw.seed if draw is not None else neg_u_order)
-    lib, s = N.lib(), N.stream_ptr(dev)
-    nu, np_, d, E = U.shape[0], P.shape[0], int(U.shape[1]), csr.num_edges
-    if P.shape[1] != d or nu != csr.n_src or np_ != csr.n_dst:
-        raise ValueError("edge_bce_loss: embedding shapes do not match the positive edges")
+    sharded = ready is not None or on_dP is not None or p_chunks is not None
+    U, P, relu_out = _loss_tables(U, P, csr, sharded)
+    dev = N.require_device(U, P, neg_u_order)
+    np_, E = P.shape[0], csr.num_edges
     if E == 0:
         # a shard without positive edges (parallel.py): its share of the loss and gradients is
         # zero, and no kernel would read a negative (the C ABI rejects the empty tensor's null
@@ -1664,91 +1640,110 @@ def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total:
         return (torch.zeros((), dtype=torch.float32, device=dev),
                 torch.zeros(U.shape, dtype=torch.float32, device=dev),
                 torch.zeros(P.shape, dtype=torch.float32, device=dev))
-    ub, pf = csr.bwd, csr.fwd
-    dU = torch.empty(U.shape, dtype=torch.float32, device=dev)
-    part = torch.empty(int(lib.hgnn_edge_score_parts(nu)), dtype=torch.float32, device=dev)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
+    negs = _Negatives.of(neg_u_order, E, np_)
     # err[0]: zeroed and counted by the scoring pass, err[1] by the int64 negatives sort
     err = torch.empty(2, dtype=torch.int32, device=dev)
     c = cscale.to(torch.float32).reshape(()).contiguous()
     inv_e = 1.0 / n_total if n_total > 0 else 0.0
-    uop = _user_of_pos(csr)
-    neg32 = neg_u_order.dtype == torch.int32          # sample_negatives' / draw_negatives' draws
-    if draw is not None:
-        if draw.n != E or draw.num_posts != np_:
-            raise ValueError("edge_bce_loss: the NegativeDraw does not match the positive edges")
-        neg = None   # drawn again where read (the sort's first pass, the scoring pass)
+    dP = _loss_dP(U, P, csr, negs, c, inv_e, err, relu_out, ready, p_chunks, presorted)
+    if on_dP is not None:
+        on_dP(dP)
+    if ready is not None and p_chunks is not None:
+        ready()                                 # all of P, for the scoring pass
+    loss, dU = _loss_scoring_pass(U, P, csr, negs, c, n_total, err if check else None)
+    if check and int(err[0]):
+        raise ValueError("edge_bce_loss: negative post id out of range")
+    return loss, dU, dP
+
+
+def _loss_tables(U, P, csr: RelationCSR, sharded: bool):
+    """``_edge_bce``'s tables checked: ``(U, P, whether U is marked a fused-ReLU output)``."""
+    relu_out = bool(getattr(U, RELU_OUT, False))   # (read here: .contiguous() may copy)
+    if U.dtype == torch.bfloat16:
+        if P.dtype != torch.bfloat16:
+            raise TypeError("edge_bce_loss: bf16 rows need both tables in bfloat16")
+        if sharded:
+            raise ValueError("edge_bce_loss: bf16 rows do not combine with ready / on_dP / "
+                             "p_chunks (the sharded step runs on fp32 rows)")
+        U, P = U.contiguous(), P.contiguous()
     else:
-        neg = neg_u_order.contiguous() if neg32 else neg_u_order.to(torch.int64).contiguous()
+        U = _check_f32(U, "edge_bce_loss user_emb")
+        P = _check_f32(P, "edge_bce_loss post_emb")
+    if P.shape[1] != U.shape[1] or U.shape[0] != csr.n_src or P.shape[0] != csr.n_dst:
+        raise ValueError("edge_bce_loss: embedding shapes do not match the positive edges")
+    return U, P, relu_out
+
+
+def _loss_dP(U, P, csr: RelationCSR, negs: _Negatives, c, inv_e, err, relu_out: bool, ready,
+             p_chunks, presorted) -> torch.Tensor:
+    """The dP chain: sort the negatives (post, user) by post, then both dP gathers in one pass,
+    each edge's weight recomputed from <U[u], P[post]> (hgnn_score_gather2); the scoring pass
+    (loss + dU) needs none of it.  ``ready`` / ``p_chunks``: see ``_edge_bce``."""
+    from .graph import NO_SPLIT, GroupedEdges, Plan
+    dev = U.device
+    np_, E, pf = P.shape[0], csr.num_edges, csr.fwd
     dP = torch.empty(P.shape, dtype=torch.float32, device=dev)
-    # dP chain: sort the negatives (post, user) by post, then the two dP gathers, each edge's
-    # weight recomputed from <U[u], P[post]> (hgnn_score_gather); pass A (loss + dU) needs none
-    # of it.
     if presorted is not None:
         presorted.check_edges(csr, np_)
         rowptr_n, nu_s = presorted.rowptr, presorted.users
     else:
-        rowptr_n, nu_s = _sort_negatives(csr, neg_u_order, draw, neg, neg32, uop, E, np_, err,
-                                         dev)
+        rowptr_n, nu_s = _sort_negatives(negs, _user_of_pos(csr), E, np_, err, dev)
     if ready is not None and p_chunks is None:
         # P is still arriving (parallel.py's all-gather of the post table): the sort above
         # needs only the edges, so it ran ahead; every kernel below reads P
         ready()
-    from .graph import NO_SPLIT, GroupedEdges, Plan
-    negs = GroupedEdges(rowptr_n, nu_s, nu_s, Plan(NO_SPLIT, 0, 0, None, None), np_)
+    no_plan = Plan(NO_SPLIT, 0, 0, None, None)
     if p_chunks is not None:
         for lo, hi, rdy in p_chunks:
             if rdy is not None:
                 rdy()
             if hi > lo:
-                ng = GroupedEdges(rowptr_n[lo:hi + 1], nu_s, None,
-                                  Plan(NO_SPLIT, 0, 0, None, None), hi - lo)
+                ng = GroupedEdges(rowptr_n[lo:hi + 1], nu_s, None, no_plan, hi - lo)
                 _score_gather2(U, P[lo:hi], _row_range(pf, lo, hi), ng, c, inv_e, dP[lo:hi])
-    else:
-        # (Measured and not kept, round 5: this gather in 8 source-block passes like K1,
-        # 32.83 vs 31.32 ms at cfg4 — each pass re-reads its rows' P vectors and dP.)
-        # A large post-ReLU U is more than half zeros: packed once (one streaming pass), the
-        # gather's 2 E row reads fetch mask + non-zeros only (HGNN_ZPACK, csrc/zpack.h).
-        Uz = None
-        if not bf16 and ready is None and zpack_on(U, relu_out):
-            Uz = zpack_rows(U)
-        _score_gather2(U, P, pf, negs, c, inv_e, dP, Uz)
-        del Uz
-    if on_dP is not None:
-        on_dP(dP)
-    if ready is not None and p_chunks is not None:
-        ready()                                 # all of P, for the scoring pass
+        return dP
+    # (Measured and not kept, round 5: this gather in 8 source-block passes like K1,
+    # 32.83 vs 31.32 ms at cfg4 — each pass re-reads its rows' P vectors and dP.)
+    # A large post-ReLU U is more than half zeros: packed once (one streaming pass), the
+    # gather's 2 E row reads fetch mask + non-zeros only (HGNN_ZPACK, csrc/zpack.h).
+    Uz = None
+    if U.dtype != torch.bfloat16 and ready is None and zpack_on(U, relu_out):
+        Uz = zpack_rows(U)
+    _score_gather2(U, P, pf, GroupedEdges(rowptr_n, nu_s, nu_s, no_plan, np_), c, inv_e, dP, Uz)
+    return dP
+
+
+def _loss_scoring_pass(U, P, csr: RelationCSR, negs: _Negatives, c, n_total: int, err):
+    """``(loss, dU)``; ``err``: where it counts out-of-range negatives, or None."""
     # (The scoring pass takes no col_hot: with the positives' cold rows read nt it measured
     # 29-33 ms against 25.4 at cfg4 for every H tried, DESIGN §5.)
+    dev = U.device
+    lib, s = N.lib(), N.stream_ptr(dev)
+    nu, np_, d, E, ub = U.shape[0], P.shape[0], int(U.shape[1]), csr.num_edges, csr.bwd
+    dU = torch.empty(U.shape, dtype=torch.float32, device=dev)
+    part = torch.empty(int(lib.hgnn_edge_score_parts(nu)), dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    head = (N.ptr(U), N.ptr(P), d, nu, np_, N.ptr(ub.rowptr), N.ptr(ub.col))
+    tail = (N.ptr(part), N.ptr(loss), N.ptr(err), s)
     rb = _row_bytes(U)     # per edge two post rows, per user its own row in and a dU row out
     with _timed(f"edge_score_d{d}", E * (2 * rb + 12) + nu * (rb + 4 * d)):
-        if bf16:
+        if U.dtype == torch.bfloat16:
             N.check(lib.hgnn_edge_score_fwd_bf16(
-                N.ptr(U), N.ptr(P), d, nu, np_, N.ptr(ub.rowptr), N.ptr(ub.col),
-                N.ptr(neg) if draw is None and not neg32 else None,
-                N.ptr(neg) if draw is None and neg32 else None,
-                N.ptr(draw.seed) if draw is not None else None, n_total, N.ptr(c), N.ptr(dU),
-                N.ptr(part), N.ptr(loss), N.ptr(err if check else None), s),
-                "hgnn_edge_score_fwd_bf16")
-        elif draw is not None:
+                *head, N.ptr(negs.i64), N.ptr(negs.i32),
+                N.ptr(negs.draw.seed if negs.draw is not None else None), n_total, N.ptr(c),
+                N.ptr(dU), *tail), "hgnn_edge_score_fwd_bf16")
+        elif negs.draw is not None:
             N.check(lib.hgnn_edge_score_fwd_draw(
-                N.ptr(U), N.ptr(P), d, nu, np_, N.ptr(ub.rowptr), N.ptr(ub.col),
-                N.ptr(draw.seed), n_total, N.ptr(c), N.ptr(dU), N.ptr(part), N.ptr(loss),
-                N.ptr(err if check else None), s), "hgnn_edge_score_fwd_draw")
-        elif neg32:
+                *head, N.ptr(negs.draw.seed), n_total, N.ptr(c), N.ptr(dU), *tail),
+                "hgnn_edge_score_fwd_draw")
+        elif negs.i32 is not None:
             N.check(lib.hgnn_edge_score_fwd_i32(
-                N.ptr(U), N.ptr(P), d, nu, np_, N.ptr(ub.rowptr), N.ptr(ub.col),
-                N.ptr(neg), n_total, N.ptr(c), N.ptr(dU), N.ptr(part), N.ptr(loss),
-                N.ptr(err if check else None), s), "hgnn_edge_score_fwd_i32")
+                *head, N.ptr(negs.i32), n_total, N.ptr(c), N.ptr(dU), *tail),
+                "hgnn_edge_score_fwd_i32")
         else:
             N.check(lib.hgnn_edge_score_fwd(
-                N.ptr(U), N.ptr(P), d, nu, np_, N.ptr(ub.rowptr), N.ptr(ub.col),
-                N.ptr(neg), None, n_total, N.ptr(c), N.ptr(dU), None, None, None, None,
-                N.ptr(part), N.ptr(loss), N.ptr(err if check else None), s),
-                "hgnn_edge_score_fwd")
-    if check and int(err[0]):
-        raise ValueError("edge_bce_loss: negative post id out of range")
-    return loss, dU, dP
+                *head, N.ptr(negs.i64), None, n_total, N.ptr(c), N.ptr(dU), None, None, None,
+                None, *tail), "hgnn_edge_score_fwd")
+    return loss, dU
 
 
 class _EdgeBCELoss(torch.autograd.Function):
@@ -1851,10 +1846,8 @@ def edge_bce_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: tor
     if bf16:
         _check_f32(user_emb, "edge_bce_loss user_emb")
         _check_f32(post_emb, "edge_bce_loss post_emb")
-        return _EdgeBCELoss.apply(user_emb, post_emb, csr, neg_u, cscale, check, n_total, ready,
-                                  presorted, True)
     return _EdgeBCELoss.apply(user_emb, post_emb, csr, neg_u, cscale, check, n_total, ready,
-                              presorted)
+                              presorted, bf16)
 
 
 def edge_bce_loss_raw(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: torch.Tensor,
