@@ -449,6 +449,17 @@ int hgnn_scale_unless_one(float* x, int64_t n, const float* d_scale, hgnn_stream
  * n_elems % 8; n_elems = 0 is fine.  x and out 16-byte aligned. */
 int hgnn_rows_to_bf16(const float* x, int64_t n_elems, uint16_t* out, hgnn_stream_t stream);
 
+/* ReLU's backward fused into the cast (opt-in bf16 gradient rows, HGNN_GRAD_ROW_DTYPE=bf16 in the
+ * Python layer): dz[r][c] = bf16(out[r][c] > 0 ? dout[r][c] : +0), rounded as hgnn_rows_to_bf16
+ * does — bitwise that cast of the dz_out hgnn_linear_bwd_dz writes, in 6 bytes per element
+ * (+ 16 B of mask per row) instead of 10.  Exactly one of out_act (the forward's [n_rows, h]
+ * output) and mask (the bits hgnn_linear_fwd_mask wrote: 4 words per row at every h, column j at
+ * bit 4 (j / 16) + j % 4 of word (j / 4) % 4) is the predicate; both or neither: HGNN_E_ARG.
+ * h % 8 == 0; with mask also h % 16 == 0 and h <= 128 (else HGNN_E_UNSUPPORTED, the message
+ * names h).  Every pointer 16-byte aligned; n_rows = 0 is fine with null pointers. */
+int hgnn_relu_grad_to_bf16(const float* dout, const float* out_act, const uint32_t* mask,
+                           int64_t n_rows, int32_t h, uint16_t* dz, hgnn_stream_t stream);
+
 /* hgnn_gather_reduce_hot and hgnn_gather_reduce_scaled in one, over a bf16 source table x:
  * edge_w / col_w / row_w (row_w replaces HGNN_MEAN, not both), HGNN_MEAN / HGNN_ACCUMULATE,
  * acc_limit, the heavy-row plan with its fp32 slab, col_hot / hot_share (all nullable as there).

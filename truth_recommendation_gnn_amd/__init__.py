@@ -5,7 +5,9 @@ reference's PyG-style Python surface (``SAGEConv``, ``HeteroData``, ``WeightedRG
 fp32 throughout by default.  ``HGNN_ROW_DTYPE=bf16`` (read at import into ``ops.ROW_DTYPE``), or
 ``row_dtype="bf16"`` on the models, ``ops.LayerSpec`` and ``ops.edge_bce_loss``, stores the rows
 the forward gathers and the link loss read per edge as bf16 (``ops.rows_to_bf16``); everything
-else stays fp32.  ``evaluate`` / ``recommend`` take their own ``row_dtype`` (default "fp32") or
+else stays fp32.  ``HGNN_GRAD_ROW_DTYPE=bf16`` (``ops.GRAD_ROW_DTYPE``; ``grad_row_dtype="bf16"``
+on the models and ``ops.LayerSpec``) is a second, independent opt-in: the backward's K2 scatters
+read bf16 copies of their gradient tables.  ``evaluate`` / ``recommend`` take their own ``row_dtype`` (default "fp32") or
 bf16 tables, and then rank the rows rounded to bf16 on bf16 MFMA.
 """
 from .graph import HeteroData, RelationCSR, relation_csr, CSR_CACHE  # noqa: F401

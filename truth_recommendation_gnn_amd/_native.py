@@ -145,6 +145,7 @@ _SIGS = {
     "hgnn_edge_score_fwd_draw": (_c_i32, [_p, _p, _c_i32, _c_i64, _c_i64, _p, _p, _p, _c_i64,
                                           _p, _p, _p, _p, _p, _p]),
     "hgnn_rows_to_bf16": (_c_i32, [_p, _c_i64, _p, _p]),
+    "hgnn_relu_grad_to_bf16": (_c_i32, [_p, _p, _p, _c_i64, _c_i32, _p, _p]),
     "hgnn_gather_reduce_bf16": (_c_i32, [_p, _c_i64, _c_i32, _p, _p, _c_i64, _p, _p, _p, _c_i32,
                                          _p, _p, _c_i64, _c_i64, _c_i32, _p, _p, _c_i64, _p,
                                          ctypes.c_float, _p]),

@@ -160,10 +160,19 @@ def _row_dtype_arg(row_dtype: Optional[str]) -> Optional[str]:
     return row_dtype
 
 
+def _grad_row_dtype_arg(grad_row_dtype: Optional[str]) -> Optional[str]:
+    """A constructor's ``grad_row_dtype``: "fp32", "bf16" or None (``ops.GRAD_ROW_DTYPE`` at each
+    call), handed to every ``ops.LayerSpec`` the model builds."""
+    if grad_row_dtype is not None:
+        ops.resolve_grad_row_dtype(grad_row_dtype)
+    return grad_row_dtype
+
+
 class _LayoutModel(torch.nn.Module):
     """A hetero SAGE layer described by a layout, run as one fused ``hetero_layer``."""
     layout: Layout
     row_dtype: Optional[str] = None
+    grad_row_dtype: Optional[str] = None
 
     def _run_layer(self, convs, x_dict, edge_index_dict, relu: bool = True):
         types = tuple(sorted(x_dict))
@@ -179,17 +188,19 @@ class _LayoutModel(torch.nn.Module):
             static = tuple(not x_dict[et[0]].requires_grad for _, et, _ in msgs)
             groups.append(ops.DstGroup(dst, tuple(rels), root, relu, static=static))
         weights = _fused_weights_layer(convs, list(self.layout.values()), x_dict)
-        return ops.hetero_layer(ops.LayerSpec(types, tuple(groups), self.row_dtype),
-                                dict(x_dict), weights)
+        return ops.hetero_layer(ops.LayerSpec(types, tuple(groups), self.row_dtype,
+                                              self.grad_row_dtype), dict(x_dict), weights)
 
 
 class WeightedRGCN(_LayoutModel):
     """``train_gnn.py:147-200``: user = relu(1.0*msg_direct + 0.75*msg_social), post =
     relu(post_update)."""
 
-    def __init__(self, hidden_dim: int = 64, row_dtype: Optional[str] = None):
+    def __init__(self, hidden_dim: int = 64, row_dtype: Optional[str] = None,
+                 grad_row_dtype: Optional[str] = None):
         super().__init__()
         self.row_dtype = _row_dtype_arg(row_dtype)
+        self.grad_row_dtype = _grad_row_dtype_arg(grad_row_dtype)
         self.msg_direct = SAGEConv((-1, -1), hidden_dim)
         self.msg_social = SAGEConv((-1, -1), hidden_dim)
         self.post_update = SAGEConv((-1, -1), hidden_dim)
@@ -213,9 +224,11 @@ class WeightedRGCN(_LayoutModel):
 class WeightedRGCNAuthor(_LayoutModel):
     """``test_gnn.py:116-168``: 3 user messages weighted 1.75 / 0.7 / 0.3."""
 
-    def __init__(self, hidden_dim: int = 64, row_dtype: Optional[str] = None):
+    def __init__(self, hidden_dim: int = 64, row_dtype: Optional[str] = None,
+                 grad_row_dtype: Optional[str] = None):
         super().__init__()
         self.row_dtype = _row_dtype_arg(row_dtype)
+        self.grad_row_dtype = _grad_row_dtype_arg(grad_row_dtype)
         self.msg_direct = SAGEConv((-1, -1), hidden_dim)
         self.msg_author = SAGEConv((-1, -1), hidden_dim)
         self.msg_social = SAGEConv((-1, -1), hidden_dim)
@@ -242,12 +255,15 @@ class HeteroSAGE(torch.nn.Module):
     stacked).  ``relations``: [(edge_type, weight)].  Parameters are named
     ``layers.{l}.{src}__{rel}__{dst}.lin_{l,r}.*``.  ``row_dtype``: the storage of the rows the
     forward gathers from layer outputs, "fp32", "bf16" or None for ``ops.ROW_DTYPE`` (layer 1's
-    static inputs keep fp32 rows either way)."""
+    static inputs keep fp32 rows either way).  ``grad_row_dtype``: the storage of the gradient
+    rows the backward's K2 scatters read, "fp32", "bf16" or None for ``ops.GRAD_ROW_DTYPE``."""
 
     def __init__(self, hidden_dim: int, relations: Sequence[Tuple[EdgeType, float]],
-                 num_layers: int = 2, in_channels: int = -1, row_dtype: Optional[str] = None):
+                 num_layers: int = 2, in_channels: int = -1, row_dtype: Optional[str] = None,
+                 grad_row_dtype: Optional[str] = None):
         super().__init__()
         self.row_dtype = _row_dtype_arg(row_dtype)
+        self.grad_row_dtype = _grad_row_dtype_arg(grad_row_dtype)
         self.hidden_dim = hidden_dim
         self.relations = [(tuple(et), float(w)) for et, w in relations]
         self.layers = torch.nn.ModuleList()
@@ -277,8 +293,8 @@ class HeteroSAGE(torch.nn.Module):
                 groups.append(ops.DstGroup(dst, rels, True, True, pre, static=static))
                 msgs_g.append(msgs)
             weights = _fused_weights_layer(convs, msgs_g, h)
-            out = ops.hetero_layer(ops.LayerSpec(types, tuple(groups), self.row_dtype), h,
-                                   weights)
+            out = ops.hetero_layer(ops.LayerSpec(types, tuple(groups), self.row_dtype,
+                                                 self.grad_row_dtype), h, weights)
             for t in h:
                 out.setdefault(t, h[t])
             h = out

@@ -57,6 +57,25 @@ def resolve_row_dtype(row_dtype: Optional[str]) -> str:
     return _row_dtype_value(ROW_DTYPE if row_dtype is None else row_dtype, "row_dtype")
 
 
+# How the backward's K2 scatters store the gradient rows they read once per edge, a second
+# opt-in independent of ROW_DTYPE.  "fp32" (the default): the fp32 gradient tables themselves.
+# "bf16": each K2 of a fused layer's backward reads a bf16 copy of its table — the K3 dgrad's
+# dA of an aggregate segment (``rows_to_bf16``), or a pre-projected relation's ReLU-masked dz
+# (``relu_grad_bf16``, the mask fused into the cast) — so every gradient the layer returns is what
+# the fp32 backward gives when each K2 reads R(T) in place of T.  K2's accumulators and outputs,
+# K3, the weight, bias and root gradients stay fp32.  Read from
+# HGNN_GRAD_ROW_DTYPE at import; a LayerSpec and the model constructors take a ``grad_row_dtype``
+# of their own, None meaning this value at call time.
+GRAD_ROW_DTYPE = _row_dtype_value(os.environ.get("HGNN_GRAD_ROW_DTYPE", "fp32"),
+                                  "HGNN_GRAD_ROW_DTYPE")
+
+
+def resolve_grad_row_dtype(grad_row_dtype: Optional[str]) -> str:
+    """``grad_row_dtype`` itself, or the module's ``GRAD_ROW_DTYPE`` (as it is now) for None."""
+    return _row_dtype_value(GRAD_ROW_DTYPE if grad_row_dtype is None else grad_row_dtype,
+                            "grad_row_dtype")
+
+
 # ----------------------------------------------------------------------------- kernel timing
 class KernelTimer:
     """Records HIP events around every kernel call this module makes (on the current stream,
@@ -145,6 +164,35 @@ def rows_to_bf16(x: torch.Tensor) -> torch.Tensor:
         N.check(N.lib().hgnn_rows_to_bf16(N.ptr(x), x.numel(), N.ptr(out), N.stream_ptr(dev)),
                 "hgnn_rows_to_bf16")
     return out
+
+
+def relu_grad_bf16(dout: torch.Tensor, out_act: Optional[torch.Tensor] = None,
+                   mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``bf16(dout * (out > 0))`` in one streaming pass (``hgnn_relu_grad_to_bf16``): ReLU's
+    backward fused into the cast, bitwise ``rows_to_bf16`` of the ``dz_out`` the K3 backward
+    writes.  The predicate is exactly one of ``out_act`` (the forward's output) and ``mask`` (its
+    ReLU bits, :func:`relu_mask_for`; 16 B read per row instead of the 4h-byte output)."""
+    dout = _check_f32(dout, "relu_grad_bf16")
+    if dout.dim() != 2:
+        raise ValueError(f"relu_grad_bf16: dout is {tuple(dout.shape)}, expected [n, h]")
+    n, h = int(dout.shape[0]), int(dout.shape[1])
+    if out_act is not None:
+        out_act = _check_f32(out_act, "relu_grad_bf16")
+        if tuple(out_act.shape) != (n, h):
+            raise ValueError(f"relu_grad_bf16: out_act is {tuple(out_act.shape)}, "
+                             f"expected {(n, h)}")
+    if mask is not None and (mask.dtype != torch.int32 or tuple(mask.shape) != (n, 4)
+                             or not mask.is_contiguous()):
+        raise ValueError(f"relu_grad_bf16: ReLU bits are {mask.dtype} {tuple(mask.shape)}, "
+                         f"expected contiguous int32 {(n, 4)}")
+    dev = N.require_device(dout, out_act, mask)
+    dz = torch.empty((n, h), dtype=torch.bfloat16, device=dev)
+    nbytes = 6 * n * h + 16 * n if mask is not None else 10 * n * h
+    with _timed(f"relu_grad_bf16[{n}]x{h}", nbytes):
+        N.check(N.lib().hgnn_relu_grad_to_bf16(N.ptr(dout), N.ptr(out_act), N.ptr(mask), n, h,
+                                               N.ptr(dz), N.stream_ptr(dev)),
+                "hgnn_relu_grad_to_bf16")
+    return dz
 
 
 def _check_table(t: torch.Tensor, what: str) -> torch.Tensor:
@@ -565,8 +613,9 @@ def _score_gather2(U, P, pos, negs, cscale, inv_e, out, Uz=None):
 
 def scatter_mean_bwd(grad_aggr: torch.Tensor, csr: RelationCSR,
                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """K2: ``grad_x_src[j] (+)= sum_{(j->i)} grad_aggr[i] / deg_i`` over the CSC."""
-    grad_aggr = _check_f32(grad_aggr, "scatter_mean_bwd")
+    """K2: ``grad_x_src[j] (+)= sum_{(j->i)} grad_aggr[i] / deg_i`` over the CSC.  ``grad_aggr``:
+    fp32, or the bf16 gradient rows of ``grad_row_dtype`` (sums and ``out`` stay fp32)."""
+    grad_aggr = _check_table(grad_aggr, "scatter_mean_bwd")
     dev = grad_aggr.device
     d = int(grad_aggr.shape[1])
     acc = out is not None
@@ -576,10 +625,11 @@ def scatter_mean_bwd(grad_aggr: torch.Tensor, csr: RelationCSR,
     if B > 1:
         passes, w = csr.blocks("bwd", B)
         E = csr.num_edges
+        rb = _row_bytes(grad_aggr)
         _gather_blocked(grad_aggr, passes, None, w, out, acc,
                         f"gather_bwd[{csr.n_src}<-{csr.n_dst}]x{d}",
-                        gather_bytes(E, csr.n_src, d, True),
-                        gather_compulsory_bytes(E, csr.n_src, csr.n_dst, d, True))
+                        gather_bytes(E, csr.n_src, d, True, rb),
+                        gather_compulsory_bytes(E, csr.n_src, csr.n_dst, d, True, rb))
         return out
     _gather(grad_aggr, csr.bwd, None, csr_mean=False, out=out, accumulate=acc,
             edge_w=csr.bwd_weights, hot=csr.hot_cols("bwd", _table_bytes(grad_aggr)))
@@ -1069,6 +1119,9 @@ class LayerSpec:
     # storage of the rows the layer's forward gathers: "fp32", "bf16", or None for ops.ROW_DTYPE
     # at call time (see ``_layer_plan``)
     row_dtype: Optional[str] = None
+    # storage of the gradient rows the layer's K2 scatters read: "fp32", "bf16", or None for
+    # ops.GRAD_ROW_DTYPE at call time (see ``_layer_plan``)
+    grad_row_dtype: Optional[str] = None
 
 
 # ----------------------------------------------------------------------------- layer plan
@@ -1088,6 +1141,7 @@ class _GroupPlan(NamedTuple):
     # gathers the projected rows, which change with the weights)
     static: Tuple[bool, ...]
     bf16: Tuple[bool, ...]          # relation i gathers the bf16 copy of its table
+    gbf16: Tuple[bool, ...]         # relation i's K2 reads the bf16 copy of its gradient table
     cols: Tuple[Tuple[int, int], ...]   # (offset, width) of relation i's lin_l block in the weight
     root_col: int                   # offset of the root block (the weight's last)
     main: Tuple[int, ...]           # the relations that are not pre-projected: the K3 segments
@@ -1103,7 +1157,7 @@ class _LayerPlan(NamedTuple):
 
 
 def _layer_plan(spec: LayerSpec, shapes: Dict[str, Tuple[int, int]], hidden: Sequence[int],
-                bf16: bool) -> _LayerPlan:
+                bf16: bool, grad_bf16: bool = False) -> _LayerPlan:
     """Every decision of one ``hetero_layer`` call, from the spec, the inputs' ``(rows,
     columns)`` by type, each group's output width and the resolved row mode; no tensor is read.
 
@@ -1111,7 +1165,13 @@ def _layer_plan(spec: LayerSpec, shapes: Dict[str, Tuple[int, int]], hidden: Seq
     projected rows of a pre-projected relation, so judged at the output width) only in a
     full-table group (a sampled block — ``n_root`` / ``root_src`` — keeps fp32 rows), never
     where the caller declared the table static (a model input is gathered once and kept,
-    whatever HGNN_STATIC_AGG says), and only at a width that is a multiple of 8."""
+    whatever HGNN_STATIC_AGG says), and only at a width that is a multiple of 8.
+
+    bf16 gradient rows (``grad_bf16``): a relation's K2 reads the bf16 copy of its gradient
+    table (dA at the segment width, or a pre-projected relation's dz at the output width) under
+    the same two rules — a full-table group, a width that is a multiple of 8 — and where it has
+    edges; whether its source needs a gradient (whether the K2 runs at all) is known only in the
+    backward."""
     groups, shadow = [], []
     for gi, g in enumerate(spec.groups):
         block = g.n_root is not None or g.root_src is not None
@@ -1139,8 +1199,10 @@ def _layer_plan(spec: LayerSpec, shapes: Dict[str, Tuple[int, int]], hidden: Seq
                             and (hidden[gi] if pre[i] else cols[i][1]) % 8 == 0) for i in R)
         shadow += [g.rels[i][0] for i in R
                    if rounds[i] and not pre[i] and g.rels[i][0] not in shadow]
+        grounds = tuple(bool(grad_bf16 and not block and g.rels[i][1].num_edges > 0
+                             and (hidden[gi] if pre[i] else cols[i][1]) % 8 == 0) for i in R)
         groups.append(_GroupPlan(g.dst, tuple(g.rels), bool(g.relu), bool(g.root), root_type,
-                                 g.n_root, n_dst, pre, static, rounds, tuple(cols), o,
+                                 g.n_root, n_dst, pre, static, rounds, grounds, tuple(cols), o,
                                  tuple(i for i in R if not pre[i])))
     return _LayerPlan(tuple(spec.types), tuple(groups), not any(any(p.pre) for p in groups),
                       tuple(shadow))
@@ -1187,13 +1249,14 @@ def _fwd_job(p: _GroupPlan, xs, aggrs, w, b) -> FwdJob:
 
 def _main_dxs(p: _GroupPlan, aggrs, need_x, pending) -> List[Optional[torch.Tensor]]:
     """The gradient buffer of each main aggregate (None where no source gradient comes of it),
-    each queued in ``pending`` for the K2 into its source type."""
+    each queued in ``pending`` for the K2 into its source type as ``(dA, csr, its K2 reads the
+    bf16 copy of dA)``."""
     dxs: List[Optional[torch.Tensor]] = []
     for i, a in zip(p.main, aggrs):
         src, csr = p.rels[i]
         if need_x[src] and csr.num_edges > 0:
             dxs.append(torch.empty_like(a))
-            pending.setdefault(src, []).append((dxs[-1], csr))
+            pending.setdefault(src, []).append((dxs[-1], csr, p.gbf16[i]))
         else:
             dxs.append(None)
     return dxs
@@ -1337,12 +1400,25 @@ class _HeteroLayer(torch.autograd.Function):
         for t in pending:
             if gx[t] is None:
                 gx[t] = torch.zeros_like(xs[t])
-        if not (len(pending) > 1 and _k2_rounds(pending, gx, prefix)):
+        # (the rounds are sampled blocks' launches, fp32 rows: never with a bf16 gradient table)
+        rounded = any(gb for items in pending.values() for _, _, gb in items)
+        if rounded or not (len(pending) > 1 and _k2_rounds(
+                {t: [(dA, csr) for dA, csr, _ in items] for t, items in pending.items()},
+                gx, prefix)):
             for t, n in prefix.items():      # (no rounds after all: zero what K2s add into)
                 gx[t][n:].zero_()
+            if rounded:                      # (pending then holds the last reference to each dA)
+                jobs.clear()
+                dxs = None
             for t, items in pending.items():
-                for dA, csr in items:
+                while items:
+                    dA, csr, gb = items.pop(0)
+                    if gb:
+                        # bf16 gradient rows: cast just before the K2 that reads them, and the
+                        # fp32 dA goes back to the allocator once the cast is enqueued
+                        dA = rows_to_bf16(dA)
                     scatter_mean_bwd(dA, csr, out=gx[t])
+                    del dA
         return (None, *[gx[t] for t in plan.types], *gwb)
 
 
@@ -1408,8 +1484,12 @@ def _pre_group_backward(g: _GroupPlan, xs, aggrs, w, dout, y, need_x, need_w, ne
     """Backward of a destination group with pre-projected relations: returns (dW, db) in the
     fused weight's column layout; source gradients go to ``gx`` / ``pending`` (K2 list)."""
     # the destination update's backward over the remaining segments also writes the masked dz
-    # that the pre-projected relations' K2 scatters (from the pass that masks it anyway)
-    dz = torch.empty_like(dout) if g.relu else dout
+    # that the pre-projected relations' K2 scatters (from the pass that masks it anyway).  With
+    # bf16 gradient rows those K2s read one bf16 dz cast straight from dout and the mask
+    # (relu_grad_bf16), and K3 writes the fp32 dz only where some relation still reads it
+    want16 = any(pre and gb for pre, gb in zip(g.pre, g.gbf16))
+    want32 = any(pre and not gb for pre, gb in zip(g.pre, g.gbf16))
+    dz = (torch.empty_like(dout) if want32 else None) if g.relu else dout
     segs = list(aggrs)
     seg_cols = [g.cols[i] for i in g.main]
     dxs = _main_dxs(g, aggrs, need_x, pending)
@@ -1436,11 +1516,19 @@ def _pre_group_backward(g: _GroupPlan, xs, aggrs, w, dout, y, need_x, need_w, ne
             dw[:, co:co + k].copy_(dw_main[:, o:o + k])
             o += k
     # pre-projected relations: dP = K2(dz) over the CSC, then P = x_src W_r^T's backward
-    for (src, csr), pre, (o, k) in zip(g.rels, g.pre, g.cols):
+    dz16 = None
+    if want16:       # once per group, however many relations read it
+        if not g.relu:
+            dz16 = rows_to_bf16(dout)
+        elif mask is not None:
+            dz16 = relu_grad_bf16(dout, mask=mask)
+        else:
+            dz16 = relu_grad_bf16(dout, out_act=y)
+    for (src, csr), pre, gb, (o, k) in zip(g.rels, g.pre, g.gbf16, g.cols):
         if not pre:
             continue
         x_src = xs[src]
-        dP = scatter_mean_bwd(dz, csr)
+        dP = scatter_mean_bwd(dz16 if gb else dz, csr)
         add = need_x[src] and gx[src] is not None   # added into the table's gradient in place
         dxp = (gx[src] if add else torch.empty_like(x_src)) if need_x[src] else None
         dwp, _ = linear_bwd([x_src], w[:, o:o + k].contiguous(), dP, None, [dxp], need_w, False,
@@ -1457,7 +1545,8 @@ def hetero_layer(spec: LayerSpec, x_dict: Dict[str, torch.Tensor],
                  ) -> Dict[str, torch.Tensor]:
     plan = _layer_plan(spec, {t: tuple(x_dict[t].shape) for t in spec.types},
                        [int(w.shape[0]) for w, _ in weights],
-                       resolve_row_dtype(spec.row_dtype) == "bf16")
+                       resolve_row_dtype(spec.row_dtype) == "bf16",
+                       resolve_grad_row_dtype(spec.grad_row_dtype) == "bf16")
     flat: List[Optional[torch.Tensor]] = [x_dict[t] for t in spec.types]
     for w, b in weights:
         flat.extend([w, b])
