@@ -8,9 +8,10 @@ within every repetition (one warm-up, then the median of --reps): the fused kern
 events, plain (hgnn_score_topk / _bf16 with ``rows``) and excluding (hgnn_score_topk_excl / _bf16),
 and the whole ``recommend`` call with and without ``exclude``.  One JSON line per subset.
 
---ref-lib NAME (repeatable) adds the plain kernel of another build of the library, a file under
-the package's lib/ (e.g. the parent commit's build copied there as libhgnn_parent.so), to the same
-alternating loop; giving the same build under two names measures the run-to-run spread.
+--ref-lib NAME (repeatable) adds the plain and the excluding kernel of another build of the
+library, a file under the package's lib/ (e.g. the parent commit's build copied there as
+libhgnn_parent.so), to the same alternating loop; giving the same build under two names measures
+the run-to-run spread.
 python scripts/recommend_bench.py [--dim 64|128] [--row-dtype fp32|bf16] [--ref-lib NAME ...]"""
 import argparse
 import ctypes
@@ -56,10 +57,12 @@ def main():
     subsets = {"random_100k": torch.randperm(n_u, device=dev, generator=gen)[:100_000],
                "top128_by_seen": torch.topk(degree, 128).indices}
     entry = "hgnn_score_topk" + ("_bf16" if bf16 else "")
+    entry_x = entry.replace("topk", "topk_excl")
     libs = {"this": N.lib()}
     for name in args.ref_lib:
         ref = ctypes.CDLL(str(N.LIB_PATH.parent / pathlib.Path(name).name))
-        getattr(ref, entry).restype, getattr(ref, entry).argtypes = N._SIGS[entry]
+        for e in (entry, entry_x):
+            getattr(ref, e).restype, getattr(ref, e).argtypes = N._SIGS[e]
         libs[name] = ref
     Pk = ops.rows_to_bf16(P) if bf16 else P
     st = torch.cuda.current_stream()
@@ -74,10 +77,10 @@ def main():
         head = (N.ptr(Uk), N.ptr(rows), n, N.ptr(Pk), C, args.dim, K)
         tail = (N.ptr(topv), N.ptr(topi), N.stream_ptr(dev))
         excl = (N.ptr(seen.rowptr), N.ptr(seen.col), N.ptr(users32))
-        launches = {f"plain[{name}]": (getattr(lib, entry), head + tail)
-                    for name, lib in libs.items()}
-        launches["excl[this]"] = (getattr(libs["this"], entry.replace("topk", "topk_excl")),
-                                  head + excl + tail)
+        launches = {}
+        for name, lib in libs.items():
+            launches[f"plain[{name}]"] = (getattr(lib, entry), head + tail)
+            launches[f"excl[{name}]"] = (getattr(lib, entry_x), head + excl + tail)
         calls = {"recommend": lambda: metrics.recommend(U, P, K, users=users,
                                                         row_dtype=args.row_dtype),
                  "recommend_exclude": lambda: metrics.recommend(U, P, K, users=users, exclude=seen,
@@ -109,8 +112,9 @@ def main():
         res["excl_over_plain"] = round(res["kernel_ms"]["excl[this]"] /
                                        res["kernel_ms"]["plain[this]"], 4)
         for name in args.ref_lib:
-            res[f"plain_over_{name}"] = round(res["kernel_ms"]["plain[this]"] /
-                                              res["kernel_ms"][f"plain[{name}]"], 4)
+            for kind in ("plain", "excl"):
+                res[f"{kind}_over_{name}"] = round(res["kernel_ms"][f"{kind}[this]"] /
+                                                   res["kernel_ms"][f"{kind}[{name}]"], 4)
         print(json.dumps(res), flush=True)
 
 

@@ -42,6 +42,21 @@ def test_header_declares_and_ctypes_binds_the_excluding_entries():
     assert "hgnn_topk_finish" in text.split("hgnn_score_topk_excl(")[0].rsplit("/*", 1)[1]
 
 
+def test_lds_bytes_entries_are_pinned():
+    """The dynamic LDS of a launch, as the two queries report it: two chunk buffers of padded rows
+    and 128 lists.  fp32: chunks of 64 rows of d + 8 dwords.  bf16: rows of d + 16 halfwords in
+    chunks of 64, or of 32 where that lets one more workgroup live on the CU (at most 4, or 3 for
+    the d = 128, 64-row kernel, and what 160 KiB hold); never more than 100 KiB."""
+    lib = N.lib()
+    # 2 * chunk * (d + 16) * 2 + 128 * L * 8 with the chunks 64, 64, 32 (d = 64), 32, 32, 64 (128)
+    bf16 = {(64, 1): 21504, (64, 11): 31744, (64, 64): 75776,
+            (128, 1): 19456, (128, 11): 29696, (128, 64): 102400}
+    for (d, L), want in bf16.items():
+        assert lib.hgnn_score_topk_lds_bytes(d, L) == 2 * 64 * (d + 8) * 4 + 128 * L * 8
+        assert lib.hgnn_score_topk_bf16_lds_bytes(d, L) == want, (d, L)
+        assert want <= 100 * 1024
+
+
 def test_cpu_tensors_are_a_value_error():
     U, P = torch.ones(3, 64), torch.ones(5, 64)
     edges = torch.tensor([[0, 1], [3, 4]])
@@ -409,6 +424,7 @@ def test_materialised_path_exact(d, K, C):
         _same(recommend(Ud, Pd, K, users=ud, exclude=seen, **kw), want)
         _same(recommend(Ud, Pd, K, exclude=seen, **kw), _reference(U, P, None, lists, K))
         _same(recommend(Ud, Pd, K, users=ud, **kw), _reference(U, P, users, none, K))
+        _same(recommend(Ud, Pd, K, **kw), _reference(U, P, None, none, K))
     _same(recommend(Ud.bfloat16(), Pd.bfloat16(), K, users=ud, exclude=seen), want)
     if d == 64:                                            # the same lists from the fused kernel
         f = recommend(Ud, Pd, 64, users=ud, exclude=seen)

@@ -259,18 +259,32 @@ __global__ void __launch_bounds__(256) k_topk_metrics(const TopkArgs a) {
 
 
 // ---- fused scoring + top-L: the score matrix is never materialised ---------------------------
-// One workgroup = 4 waves x 32 users; the candidates stream through LDS in chunks of TC rows
+// One kernel body, k_score_topk, for fp32 and bf16 rows; a format policy (StF32 / StB16, below)
+// supplies the element type, the shape of the workgroup and the MFMA of one k-step.
+// One workgroup = 128 users; the candidates stream through LDS in chunks of TC rows
 // (double-buffered, next chunk prefetched into registers during the MFMA work of the current one).
-// Scores come from fp32 MFMA 16x16x4 with the candidates as the A operand (rows) and the users as
-// B (columns), so each lane ends with 4 candidates x 1 user per 16x16 tile and compares them with
-// ONE threshold, its user's current L-th value.  Candidates that pass go, one at a time, into the
-// user's list in LDS (entry r on lane r: the same sorted-list insert as WaveTopL).  A 16x16 tile
-// of scores costs D/4 MFMAs; the rejection test costs one max3 + one compare per lane.
-constexpr int kStUsersPerWave = 32;
-constexpr int kStWaves = 4;
-constexpr int kStThreads = kStWaves * 64;
+// The candidates are the A operand (rows) of a 16x16 MFMA tile and the users B (columns): lane
+// (i, g) holds one 16-B piece per k-step of row i (k = 4 EPP c + EPP g + j), and the C/D mapping
+// (col = lane & 15, row = 4 (lane >> 4) + reg) gives each lane 4 candidates x 1 user per tile, so
+// it compares them with ONE threshold, its user's current L-th value.  Candidates that pass go,
+// one at a time, into the user's list in LDS (entry r on lane r: the same sorted-list insert as
+// WaveTopL).  The rejection test costs one max3 + one compare per lane.
+// fp32 rows (StF32): 4 waves x 32 users (two user tiles per wave), chunks of 64, scores on
+// v_mfma_f32_16x16x4_f32: a tile costs D/4 MFMAs of 32 cycles.  LDS rows are D + 8 dwords.
+// bf16 rows (StB16; U and P are uint16_t bit patterns): scores on v_mfma_f32_16x16x32_bf16;
+// products are exact and the accumulation is fp32, so a score is the fp32 dot product of the
+// widened rows up to summation order.  A tile costs D/32 MFMAs of 16 cycles, and what is left is
+// the inserts: a chain of LDS reads, a ballot, shuffles and LDS writes per entry, one entry at a
+// time per wave.  Only more waves hide that latency, so a wave takes ONE 16-user tile and a
+// workgroup is 8 waves; wider waves (32 / 64 users) and wider workgroups (256 / 512 users), which
+// would cut the candidate stream, all measured slower.  For the same reason the
+// chunk shrinks from 64 to 32 candidates where the smaller buffers let one more workgroup live on
+// the CU (st16_chunk).  LDS rows are D + 16 halfwords: consecutive rows sit 32 B apart mod 256,
+// which is conflict-free for the ds_read_b128 fragment reads under their lane groups ({0-3, 12-15,
+// 20-27}, ...); a pad of 8 halfwords (16 B) would leave them 2-way (the K3 planes).
+constexpr int kStUsers = 128;   // per workgroup, both formats
 
-// Per-row exclusion lists (the EXCL instantiations of the two kernels below): output row r never
+// Per-row exclusion lists (the EXCL instantiations of the kernel below): output row r never
 // lists the candidates col[rowptr[e] .. rowptr[e + 1]), e = rows ? rows[r] : r, each list strictly
 // ascending.  One lane per user of the wave's tile owns that user's list: a cursor, the two entries
 // under it (held in registers: a chunk without excluded candidates costs no load, and the entry a
@@ -333,10 +347,10 @@ struct StExclCursor {
 };
 
 struct ScoreTopkArgs {
-  const float* U;         // [n_u_rows][d] user embeddings
+  const void* U;          // [n_u_rows][d] user embeddings, the format's elements
   const int32_t* rows;    // null, or the U row of each output row
   int64_t n_rows;
-  const float* P;         // [>= n_cand][d] candidate embeddings
+  const void* P;          // [>= n_cand][d] candidate embeddings
   int64_t n_cand;
   int32_t L;              // list length, 1..64
   float* topv;            // [n_rows][L] scores, best first
@@ -344,13 +358,67 @@ struct ScoreTopkArgs {
   StExcl x;               // read by the excluding instantiations only
 };
 
-template <int D>
-struct StCfg {
-  static constexpr int TC = 64;              // candidates per chunk
-  static constexpr int S = D + 8;            // LDS row stride (dwords): b128 fragment reads
-  static constexpr int KC = D / 16;          // float4 fragments per row per lane
-  static constexpr int LOADS = TC * D / 4 / kStThreads;   // float4 per thread per chunk
+typedef short st_bf16x8 __attribute__((ext_vector_type(8)));
+
+constexpr size_t kSt16LdsLimit = 160 * 1024;      // one CU's LDS
+
+#ifndef HGNN_ST16_TC
+#define HGNN_ST16_TC 0    // A/B builds: 32 / 64 forces the bf16 chunk
+#endif
+
+// two chunk buffers of tc padded rows + the lists
+template <class F>
+constexpr size_t st_lds_bytes(int d, int L, int tc) {
+  return (size_t)2 * tc * (d + F::PAD) * sizeof(typename F::Elem) + (size_t)kStUsers * L * 8;
+}
+
+inline int st16_chunk(int d, int L, bool excl);
+
+// What a format supplies: Elem and Frag (one lane's 16-B piece of a row: EPP elements, one
+// k-step's operand), WAVES per workgroup, NT 16-user tiles per wave (WAVES x NT x 16 = kStUsers),
+// PAD elements behind each LDS row, TC_MIN (the smallest chunk it launches) and chunk(), zero()
+// and mma(): acc += candidates' piece x users' piece over the piece's EPP columns.
+struct StF32 {
+  using Elem = float;
+  using Frag = float4;
+  static constexpr int EPP = 4, WAVES = 4, NT = 2, PAD = 8, TC_MIN = 64;
+  static int chunk(int, int, bool) { return 64; }
+  static __device__ __forceinline__ Frag zero() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+  static __device__ __forceinline__ f32x4 mma(const Frag& p, const Frag& u, f32x4 acc) {
+    acc = mfma4(p.x, u.x, acc);
+    acc = mfma4(p.y, u.y, acc);
+    acc = mfma4(p.z, u.z, acc);
+    return mfma4(p.w, u.w, acc);
+  }
 };
+
+struct StB16 {
+  using Elem = uint16_t;
+  using Frag = st_bf16x8;
+  static constexpr int EPP = 8, WAVES = 8, NT = 1, PAD = 16, TC_MIN = 32;
+  static int chunk(int d, int L, bool excl) { return st16_chunk(d, L, excl); }
+  static __device__ __forceinline__ Frag zero() { return Frag{0, 0, 0, 0, 0, 0, 0, 0}; }
+  static __device__ __forceinline__ f32x4 mma(const Frag& p, const Frag& u, f32x4 acc) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(p, u, acc, 0, 0, 0);
+  }
+};
+
+// Workgroups of this (d, L, chunk) that fit a CU: by LDS, and by wave slots (4 x 8 waves fill the
+// CU's 32; the d = 128, 64-candidate kernel holds 70 VGPRs, 7 waves per SIMD: 3 workgroups).
+// The excluding kernels hold the cursor and the chunk's mask on top: 63 VGPRs at (64, 32) and at
+// (64, 64), 72 at (128, 32), 78 at (128, 64).  The caps are those the chunks were measured with,
+// when (64, 64) held 71 and 7 waves per SIMD; it now fits 8, and its cap has not been re-tuned.
+inline int st16_resident(int d, int L, int tc, bool excl) {
+  const int by_lds = (int)(kSt16LdsLimit / st_lds_bytes<StB16>(d, L, tc));
+  const int cap = excl ? ((d == 64 && tc == 32) ? 4 : 3) : ((d == 128 && tc == 64) ? 3 : 4);
+  return by_lds < cap ? by_lds : cap;
+}
+
+// Candidates per chunk: 64 (half the barriers), or 32 where that makes room for a workgroup more.
+inline int st16_chunk(int d, int L, bool excl) {
+  if (HGNN_ST16_TC == 32 || HGNN_ST16_TC == 64) return HGNN_ST16_TC;
+  return st16_resident(d, L, 32, excl) > st16_resident(d, L, 64, excl) ? 32 : 64;
+}
 
 __device__ __forceinline__ void st_insert(float* lvs, int* lis, int L, int lane, float cs, int ci,
                                           float& newthr) {
@@ -369,58 +437,70 @@ __device__ __forceinline__ void st_insert(float* lvs, int* lis, int L, int lane,
 
 // The write-out of the lists: with exclusions a row can end with fewer than L entries, and its
 // empty slots (the in-LDS sentinel) leave as score -inf, index -1.
-template <int D, bool EXCL>
-__global__ void __launch_bounds__(kStThreads) k_score_topk(const ScoreTopkArgs a) {
-  using Cfg = StCfg<D>;
-  constexpr int TC = Cfg::TC, S = Cfg::S, KC = Cfg::KC, LOADS = Cfg::LOADS;
+template <class F, int D, int TC, bool EXCL>
+__global__ void __launch_bounds__(F::WAVES * 64) k_score_topk(const ScoreTopkArgs a) {
+  using Elem = typename F::Elem;
+  using Frag = typename F::Frag;
+  constexpr int EPP = F::EPP, NT = F::NT;
+  constexpr int THREADS = F::WAVES * 64;
+  constexpr int UW = NT * 16;                   // users per wave
+  constexpr int S = D + F::PAD;                 // LDS row stride, elements: b128 fragment reads
+  constexpr int KC = D / (4 * EPP);             // k-steps (fragments per row per lane) per tile
+  constexpr int MT = 2;                         // tiles whose MFMA chains interleave (4: slower)
+  constexpr int PIECES = TC * D / EPP;          // 16-B pieces per chunk
+  constexpr int LOADS = (PIECES + THREADS - 1) / THREADS;
+  constexpr bool FULL = PIECES % THREADS == 0;  // every thread stages LOADS pieces
+  static_assert(F::WAVES * UW == kStUsers && sizeof(Frag) == 16 && sizeof(Elem) * EPP == 16);
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* cbuf = lds;                                   // [2][TC][S]
-  float* lv_all = lds + 2 * TC * S;                    // [4 waves][32 users][L]
+  Elem* cbuf = reinterpret_cast<Elem*>(lds);                            // [2][TC][S]
+  float* lv_all = reinterpret_cast<float*>(cbuf + 2 * TC * S);          // [WAVES][UW users][L]
   const int L = a.L;
-  int* li_all = reinterpret_cast<int*>(lv_all + kStWaves * kStUsersPerWave * L);
+  int* li_all = reinterpret_cast<int*>(lv_all + kStUsers * L);
+  const Elem* U = static_cast<const Elem*>(a.U);
+  const Elem* P = static_cast<const Elem*>(a.P);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int i = lane & 15, g = lane >> 4;
-  const int64_t row0 = (int64_t)blockIdx.x * (kStWaves * kStUsersPerWave) +
-                       wave * kStUsersPerWave;
-  float* lvw = lv_all + wave * kStUsersPerWave * L;
-  int* liw = li_all + wave * kStUsersPerWave * L;
-  for (int e = lane; e < kStUsersPerWave * L; e += 64) { lvw[e] = -FLT_MAX; liw[e] = INT_MAX; }
-  // user fragments (B operand): lane (i, g) holds user i's columns 16c + 4g .. +3
-  float4 uf[2][KC];
-  float thr[2];
+  const int64_t row0 = (int64_t)blockIdx.x * kStUsers + wave * UW;
+  float* lvw = lv_all + wave * UW * L;
+  int* liw = li_all + wave * UW * L;
+  for (int e = lane; e < UW * L; e += 64) { lvw[e] = -FLT_MAX; liw[e] = INT_MAX; }
+  // user fragments (B operand): lane (i, g) holds user i's columns 4 EPP c + EPP g .. + EPP - 1
+  Frag uf[NT][KC];
+  float thr[NT];
 #pragma unroll
-  for (int nt = 0; nt < 2; ++nt) {
+  for (int nt = 0; nt < NT; ++nt) {
     const int64_t r = row0 + nt * 16 + i;
     const bool ok = r < a.n_rows;
     const int64_t ur = ok ? (a.rows ? (int64_t)a.rows[r] : r) : 0;
 #pragma unroll
     for (int c = 0; c < KC; ++c)
-      uf[nt][c] = ok ? *reinterpret_cast<const float4*>(a.U + ur * D + c * 16 + 4 * g)
-                     : make_float4(0.f, 0.f, 0.f, 0.f);
+      uf[nt][c] = ok ? *reinterpret_cast<const Frag*>(U + ur * D + c * 4 * EPP + EPP * g)
+                     : F::zero();
     thr[nt] = ok ? -FLT_MAX : FLT_MAX;   // rows past the end never take anything
   }
   const int64_t C = a.n_cand;
   const int64_t n_chunks = (C + TC - 1) / TC;
-  StExclCursor xc;   // lane u < 32 owns user u of the wave
-  if constexpr (EXCL) xc.open(a.x, lane < kStUsersPerWave && row0 + lane < a.n_rows, row0 + lane);
-  // chunk staging: thread t loads float4 number t + kStThreads q of the chunk (row-major TC x D)
-  float4 nxt[LOADS];
+  StExclCursor xc;   // lane u < UW owns user u of the wave
+  if constexpr (EXCL) xc.open(a.x, lane < UW && row0 + lane < a.n_rows, row0 + lane);
+  // chunk staging: thread t loads 16-B piece t + THREADS q of the chunk (row-major TC x D)
+  uint4 nxt[LOADS];
   auto load_chunk = [&](int64_t ch) {
 #pragma unroll
     for (int q = 0; q < LOADS; ++q) {
-      const int f = threadIdx.x + kStThreads * q;
-      const int rr = f / (D / 4), cc = (f % (D / 4)) * 4;
+      const int f = threadIdx.x + THREADS * q;
+      const int rr = f / (D / EPP), cc = (f % (D / EPP)) * EPP;
       const int64_t cand = ch * TC + rr;
-      nxt[q] = cand < C ? *reinterpret_cast<const float4*>(a.P + cand * D + cc)
-                        : make_float4(0.f, 0.f, 0.f, 0.f);
+      nxt[q] = ((FULL || f < PIECES) && cand < C)
+                   ? *reinterpret_cast<const uint4*>(P + cand * D + cc)
+                   : make_uint4(0u, 0u, 0u, 0u);
     }
   };
   auto store_chunk = [&](int buf) {
 #pragma unroll
     for (int q = 0; q < LOADS; ++q) {
-      const int f = threadIdx.x + kStThreads * q;
-      const int rr = f / (D / 4), cc = (f % (D / 4)) * 4;
-      *reinterpret_cast<float4*>(cbuf + buf * TC * S + rr * S + cc) = nxt[q];
+      const int f = threadIdx.x + THREADS * q;
+      const int rr = f / (D / EPP), cc = (f % (D / EPP)) * EPP;
+      if (FULL || f < PIECES) *reinterpret_cast<uint4*>(cbuf + buf * TC * S + rr * S + cc) = nxt[q];
     }
   };
   load_chunk(0);
@@ -431,50 +511,49 @@ __global__ void __launch_bounds__(kStThreads) k_score_topk(const ScoreTopkArgs a
     bool anyx = false;   // wave-uniform: some user of the wave excludes a candidate of this chunk
     if constexpr (EXCL) anyx = xc.template advance<TC>(a.x, ch, C);
     if (ch + 1 < n_chunks) load_chunk(ch + 1);   // in flight during the MFMA work below
-    uint32_t xlo[2] = {0u, 0u}, xhi[2] = {0u, 0u};   // the masks of this lane's two users
+    uint32_t xlo[NT] = {}, xhi[NT] = {};         // the masks of this lane's users
     if constexpr (EXCL) {
       if (anyx) {
-        xc.template fetch<TC>(i, xlo[0], xhi[0]);
-        xc.template fetch<TC>(16 + i, xlo[1], xhi[1]);
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) xc.template fetch<TC>(nt * 16 + i, xlo[nt], xhi[nt]);
       }
     }
-    const float* cb = cbuf + buf * TC * S;
+    const Elem* cb = cbuf + buf * TC * S;
+    const bool ragged = (ch + 1) * TC > C;       // only the last chunk can hold rows past C
 #pragma unroll
-    for (int t = 0; t < TC / 16; t += 2) {
-      f32x4 acc[2][2];
+    for (int t = 0; t < TC / 16; t += MT) {
+      f32x4 acc[MT][NT];
 #pragma unroll
-      for (int tt = 0; tt < 2; ++tt)
+      for (int tt = 0; tt < MT; ++tt)
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt) acc[tt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int nt = 0; nt < NT; ++nt) acc[tt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int c = 0; c < KC; ++c) {
-        float4 pv[2];
+        Frag pv[MT];
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-          pv[tt] = *reinterpret_cast<const float4*>(cb + ((t + tt) * 16 + i) * S + c * 16 + 4 * g);
+        for (int tt = 0; tt < MT; ++tt)
+          pv[tt] = *reinterpret_cast<const Frag*>(cb + ((t + tt) * 16 + i) * S + c * 4 * EPP +
+                                                  EPP * g);
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
+        for (int tt = 0; tt < MT; ++tt)
 #pragma unroll
-          for (int nt = 0; nt < 2; ++nt) {
-            acc[tt][nt] = mfma4(pv[tt].x, uf[nt][c].x, acc[tt][nt]);
-            acc[tt][nt] = mfma4(pv[tt].y, uf[nt][c].y, acc[tt][nt]);
-            acc[tt][nt] = mfma4(pv[tt].z, uf[nt][c].z, acc[tt][nt]);
-            acc[tt][nt] = mfma4(pv[tt].w, uf[nt][c].w, acc[tt][nt]);
-          }
+          for (int nt = 0; nt < NT; ++nt) acc[tt][nt] = F::mma(pv[tt], uf[nt][c], acc[tt][nt]);
       }
       // lane (i, g): acc[tt][nt][j] = score(candidate ch*TC + (t+tt)*16 + 4g + j, user nt*16 + i)
 #pragma unroll
-      for (int tt = 0; tt < 2; ++tt) {
-        const int64_t cbase = ch * TC + (t + tt) * 16 + 4 * g;
+      for (int tt = 0; tt < MT; ++tt) {
+        if (ragged) {   // wave-uniform
+          const int64_t cbase = ch * TC + (t + tt) * 16 + 4 * g;
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
+          for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (cbase + j >= C) acc[tt][nt][j] = -__builtin_inff();   // never >= any thr
+            for (int j = 0; j < 4; ++j)
+              if (cbase + j >= C) acc[tt][nt][j] = -__builtin_inff();   // never >= any thr
+        }
         if constexpr (EXCL) {
           if (anyx) {
 #pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
+            for (int nt = 0; nt < NT; ++nt) {
               const uint32_t xb = StExclCursor::tile_bits(xlo[nt], xhi[nt], t + tt, g);
 #pragma unroll
               for (int j = 0; j < 4; ++j)
@@ -484,13 +563,13 @@ __global__ void __launch_bounds__(kStThreads) k_score_topk(const ScoreTopkArgs a
         }
         bool any = false;
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt) {
+        for (int nt = 0; nt < NT; ++nt) {
           const f32x4 v = acc[tt][nt];
           any |= fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])) >= thr[nt];
         }
         if (__ballot(any) == 0ull) continue;   // wave-uniform: the common case
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
+        for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const float val = acc[tt][nt][j];
@@ -516,7 +595,7 @@ __global__ void __launch_bounds__(kStThreads) k_score_topk(const ScoreTopkArgs a
     }
   }
   // write the lists
-  for (int u = 0; u < kStUsersPerWave; ++u) {
+  for (int u = 0; u < UW; ++u) {
     const int64_t r = row0 + u;
     if (r >= a.n_rows) break;
     if (lane < L) {
@@ -527,218 +606,6 @@ __global__ void __launch_bounds__(kStThreads) k_score_topk(const ScoreTopkArgs a
       a.topi[r * L + lane] = x;
     }
   }
-}
-
-// ---- the same on bf16 rows: scores on v_mfma_f32_16x16x32_bf16 ------------------------------
-// U and P are bf16 tables (uint16_t bit patterns); products are exact and the accumulation is
-// fp32, so a score is the fp32 dot product of the widened rows up to summation order.  Candidates
-// are again the A operand and users the B operand: lane (i, g) holds 8 consecutive k of row i
-// (k = 32c + 8g + j, one 16-B read per k-step), and the C/D mapping (col = lane & 15,
-// row = 4 (lane >> 4) + reg) gives each lane 4 candidates x 1 user per tile, so the rejection
-// test and the list inserts are those of k_score_topk.
-// A tile costs D/32 MFMAs of 16 cycles instead of D/4 of 32, and what is left is the inserts: a
-// chain of LDS reads, a ballot, shuffles and LDS writes per entry, one entry at a time per wave.
-// Only more waves hide that latency, so a wave takes ONE 16-user tile (half the fp32 kernel's 32)
-// and a workgroup is 8 waves = 128 users; wider waves (32 / 64 users) and wider workgroups (256 /
-// 512 users), which would cut the candidate stream, all measured slower.  For the
-// same reason the chunk shrinks from 64 to 32 candidates where the smaller buffers let one more
-// workgroup live on the CU (st16_chunk).
-// LDS rows are D + 16 halfwords: consecutive rows sit 32 B apart mod 256, which is conflict-free
-// for the ds_read_b128 fragment reads under their lane groups ({0-3, 12-15, 20-27}, ...); a pad
-// of 8 halfwords (16 B) would leave them 2-way (the K3 planes).
-typedef short st_bf16x8 __attribute__((ext_vector_type(8)));
-
-struct ScoreTopkBf16Args {
-  const uint16_t* U;      // [n_u_rows][d] user embeddings, bf16
-  const int32_t* rows;    // null, or the U row of each output row
-  int64_t n_rows;
-  const uint16_t* P;      // [>= n_cand][d] candidate embeddings, bf16
-  int64_t n_cand;
-  int32_t L;              // list length, 1..64
-  float* topv;            // [n_rows][L] scores, best first
-  int32_t* topi;          // [n_rows][L] candidate indices
-  StExcl x;               // read by the excluding instantiations only
-};
-
-constexpr int kSt16Waves = 8;
-constexpr int kSt16Threads = kSt16Waves * 64;
-constexpr int kSt16Users = kSt16Waves * 16;        // per workgroup
-constexpr size_t kSt16LdsLimit = 160 * 1024;      // one CU's LDS
-
-#ifndef HGNN_ST16_TC
-#define HGNN_ST16_TC 0    // A/B builds: 32 / 64 forces the chunk
-#endif
-
-// two chunk buffers of tc padded rows + the lists
-constexpr size_t st16_lds_bytes(int d, int L, int tc) {
-  return (size_t)2 * tc * (d + 16) * 2 + (size_t)kSt16Users * L * 8;
-}
-
-// Workgroups of this (d, L, chunk) that fit a CU: by LDS, and by wave slots (4 x 8 waves fill the
-// CU's 32; the d = 128, 64-candidate kernel holds 68 VGPRs, 7 waves per SIMD: 3 workgroups).
-// The excluding kernels hold the cursor and the chunk's mask on top: 63 VGPRs at (64, 32), 71 at
-// (64, 64), 72 at (128, 32), 80 at (128, 64), so only the first keeps 8 waves per SIMD.
-inline int st16_resident(int d, int L, int tc, bool excl) {
-  const int by_lds = (int)(kSt16LdsLimit / st16_lds_bytes(d, L, tc));
-  const int cap = excl ? ((d == 64 && tc == 32) ? 4 : 3) : ((d == 128 && tc == 64) ? 3 : 4);
-  return by_lds < cap ? by_lds : cap;
-}
-
-// Candidates per chunk: 64 (half the barriers), or 32 where that makes room for a workgroup more.
-inline int st16_chunk(int d, int L, bool excl) {
-  if (HGNN_ST16_TC == 32 || HGNN_ST16_TC == 64) return HGNN_ST16_TC;
-  return st16_resident(d, L, 32, excl) > st16_resident(d, L, 64, excl) ? 32 : 64;
-}
-
-template <int D, int TC, bool EXCL>
-__global__ void __launch_bounds__(kSt16Threads) k_score_topk_bf16(const ScoreTopkBf16Args a) {
-  constexpr int S = D + 16;                     // LDS row stride, halfwords
-  constexpr int KS = D / 32;                    // k-steps (MFMAs) per tile
-  constexpr int MT = 2;                         // tiles whose MFMA chains interleave (4: slower)
-  constexpr int PIECES = TC * D / 8;            // 16-B pieces per chunk
-  constexpr int LOADS = (PIECES + kSt16Threads - 1) / kSt16Threads;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  uint16_t* cbuf = reinterpret_cast<uint16_t*>(lds);                    // [2][TC][S]
-  float* lv_all = reinterpret_cast<float*>(cbuf + 2 * TC * S);          // [8 waves][16 users][L]
-  const int L = a.L;
-  int* li_all = reinterpret_cast<int*>(lv_all + kSt16Users * L);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int i = lane & 15, g = lane >> 4;
-  const int64_t row0 = (int64_t)blockIdx.x * kSt16Users + wave * 16;
-  float* lvw = lv_all + wave * 16 * L;
-  int* liw = li_all + wave * 16 * L;
-  for (int e = lane; e < 16 * L; e += 64) { lvw[e] = -FLT_MAX; liw[e] = INT_MAX; }
-  // user fragments (B operand): lane (i, g) holds user i's columns 32c + 8g .. +7
-  st_bf16x8 uf[KS];
-  float thr;
-  {
-    const int64_t r = row0 + i;
-    const bool ok = r < a.n_rows;
-    const int64_t ur = ok ? (a.rows ? (int64_t)a.rows[r] : r) : 0;
-#pragma unroll
-    for (int c = 0; c < KS; ++c)
-      uf[c] = ok ? *reinterpret_cast<const st_bf16x8*>(a.U + ur * D + c * 32 + 8 * g)
-                 : st_bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-    thr = ok ? -FLT_MAX : FLT_MAX;   // rows past the end never take anything
-  }
-  const int64_t C = a.n_cand;
-  const int64_t n_chunks = (C + TC - 1) / TC;
-  StExclCursor xc;   // lane u < 16 owns user u of the wave
-  if constexpr (EXCL) xc.open(a.x, lane < 16 && row0 + lane < a.n_rows, row0 + lane);
-  // chunk staging: thread t loads 16-B piece t + 512 q of the chunk (row-major TC x D)
-  uint4 nxt[LOADS];
-  auto load_chunk = [&](int64_t ch) {
-#pragma unroll
-    for (int q = 0; q < LOADS; ++q) {
-      const int f = threadIdx.x + kSt16Threads * q;
-      const int rr = f / (D / 8), cc = (f % (D / 8)) * 8;
-      const int64_t cand = ch * TC + rr;
-      nxt[q] = (f < PIECES && cand < C) ? *reinterpret_cast<const uint4*>(a.P + cand * D + cc)
-                                        : make_uint4(0u, 0u, 0u, 0u);
-    }
-  };
-  auto store_chunk = [&](int buf) {
-#pragma unroll
-    for (int q = 0; q < LOADS; ++q) {
-      const int f = threadIdx.x + kSt16Threads * q;
-      const int rr = f / (D / 8), cc = (f % (D / 8)) * 8;
-      if (f < PIECES) *reinterpret_cast<uint4*>(cbuf + buf * TC * S + rr * S + cc) = nxt[q];
-    }
-  };
-  load_chunk(0);
-  store_chunk(0);
-  __syncthreads();
-  for (int64_t ch = 0; ch < n_chunks; ++ch) {
-    const int buf = (int)(ch & 1);
-    bool anyx = false;   // wave-uniform: some user of the wave excludes a candidate of this chunk
-    if constexpr (EXCL) anyx = xc.template advance<TC>(a.x, ch, C);
-    if (ch + 1 < n_chunks) load_chunk(ch + 1);   // in flight during the work below
-    uint32_t xlo = 0u, xhi = 0u;   // the mask of this lane's user
-    if constexpr (EXCL) {
-      if (anyx) xc.template fetch<TC>(i, xlo, xhi);
-    }
-    const uint16_t* cb = cbuf + buf * TC * S;
-    const bool ragged = (ch + 1) * TC > C;       // only the last chunk can hold rows past C
-#pragma unroll
-    for (int t = 0; t < TC / 16; t += MT) {
-      f32x4 acc[MT];
-#pragma unroll
-      for (int tt = 0; tt < MT; ++tt) acc[tt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int c = 0; c < KS; ++c) {
-        st_bf16x8 pv[MT];
-#pragma unroll
-        for (int tt = 0; tt < MT; ++tt)
-          pv[tt] = *reinterpret_cast<const st_bf16x8*>(cb + ((t + tt) * 16 + i) * S + c * 32 +
-                                                       8 * g);
-#pragma unroll
-        for (int tt = 0; tt < MT; ++tt)
-          acc[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pv[tt], uf[c], acc[tt], 0, 0, 0);
-      }
-      // lane (i, g): acc[tt][j] = score(candidate ch*TC + (t+tt)*16 + 4g + j, user i)
-#pragma unroll
-      for (int tt = 0; tt < MT; ++tt) {
-        if (ragged) {   // wave-uniform
-          const int64_t cbase = ch * TC + (t + tt) * 16 + 4 * g;
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (cbase + j >= C) acc[tt][j] = -__builtin_inff();   // never >= any thr
-        }
-        if constexpr (EXCL) {
-          if (anyx) {
-            const uint32_t xb = StExclCursor::tile_bits(xlo, xhi, t + tt, g);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-              if (xb >> j & 1u) acc[tt][j] = -__builtin_inff();
-          }
-        }
-        const f32x4 v = acc[tt];
-        const bool any = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])) >= thr;
-        if (__ballot(any) == 0ull) continue;   // wave-uniform: the common case
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float val = v[j];
-          unsigned long long cm = __ballot(val >= thr);
-          while (cm) {
-            const int src = __ffsll((long long)cm) - 1;
-            const int u = src & 15;
-            const float cs = __shfl(val, src, 64);
-            const int ci = (int)(ch * TC + (t + tt) * 16 + 4 * (src >> 4) + j);
-            float nthr;
-            st_insert(lvw + u * L, liw + u * L, L, lane, cs, ci, nthr);
-            if (i == u) thr = fmaxf(thr, nthr);
-            cm = __ballot(val >= thr) & (~0ull << src << 1);
-          }
-        }
-      }
-    }
-    if (ch + 1 < n_chunks) {
-      // the other buffer held chunk ch - 1, which every wave finished before the barrier that
-      // ended the previous iteration: one barrier per chunk
-      store_chunk(buf ^ 1);
-      __syncthreads();
-    }
-  }
-  // write the lists
-  for (int u = 0; u < 16; ++u) {
-    const int64_t r = row0 + u;
-    if (r >= a.n_rows) break;
-    if (lane < L) {
-      float v = lvw[u * L + lane];
-      int x = liw[u * L + lane];
-      if (EXCL && x == INT_MAX) { v = -__builtin_inff(); x = -1; }   // an empty slot
-      a.topv[r * L + lane] = v;
-      a.topi[r * L + lane] = x;
-    }
-  }
-}
-
-template <int D, bool EXCL>
-static void launch_score_topk_bf16(int tc, unsigned blocks, size_t lds, hipStream_t stream,
-                                   const ScoreTopkBf16Args& a) {
-  const dim3 grid(blocks), block(kSt16Threads);
-  if (tc == 32) hipLaunchKernelGGL((k_score_topk_bf16<D, 32, EXCL>), grid, block, lds, stream, a);
-  else hipLaunchKernelGGL((k_score_topk_bf16<D, 64, EXCL>), grid, block, lds, stream, a);
 }
 
 // The checks hgnn_score_topk, hgnn_score_topk_bf16 and their excluding forms share; *empty is set
@@ -760,37 +627,34 @@ static int score_topk_check(const char* what, const void* U, int64_t n_rows, con
   return HGNN_OK;
 }
 
-template <bool EXCL>
-static int score_topk_f32(const char* what, const float* U, const int32_t* rows, int64_t n_rows,
-                          const float* P, int64_t n_cand, int32_t d, int32_t L, const StExcl& x,
-                          float* topv, int32_t* topi, hipStream_t stream) {
-  bool empty;
-  const int rc = score_topk_check(what, U, n_rows, P, n_cand, d, L, topv, topi,
-                                  EXCL ? &x : nullptr, &empty);
-  if (rc != HGNN_OK || empty) return rc;
-  ScoreTopkArgs a{U, rows, n_rows, P, n_cand, L, topv, topi, x};
-  const size_t lds = hgnn_score_topk_lds_bytes(d, L);
-  const dim3 grid((unsigned)cdiv(n_rows, kStWaves * kStUsersPerWave)), block(kStThreads);
-  if (d == 64) hipLaunchKernelGGL((k_score_topk<64, EXCL>), grid, block, lds, stream, a);
-  else hipLaunchKernelGGL((k_score_topk<128, EXCL>), grid, block, lds, stream, a);
-  return check_launch("k_score_topk");
+template <class F, int D, bool EXCL>
+static void launch_score_topk(int tc, dim3 grid, size_t lds, hipStream_t stream,
+                              const ScoreTopkArgs& a) {
+  const dim3 block(F::WAVES * 64);
+  if constexpr (F::TC_MIN == 32) {
+    if (tc == 32) {
+      hipLaunchKernelGGL((k_score_topk<F, D, 32, EXCL>), grid, block, lds, stream, a);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((k_score_topk<F, D, 64, EXCL>), grid, block, lds, stream, a);
 }
 
-template <bool EXCL>
-static int score_topk_b16(const char* what, const uint16_t* U, const int32_t* rows,
-                          int64_t n_rows, const uint16_t* P, int64_t n_cand, int32_t d, int32_t L,
-                          const StExcl& x, float* topv, int32_t* topi, hipStream_t stream) {
+template <class F, bool EXCL>
+static int score_topk(const char* what, const void* U, const int32_t* rows, int64_t n_rows,
+                      const void* P, int64_t n_cand, int32_t d, int32_t L, const StExcl& x,
+                      float* topv, int32_t* topi, hipStream_t stream) {
   bool empty;
   const int rc = score_topk_check(what, U, n_rows, P, n_cand, d, L, topv, topi,
                                   EXCL ? &x : nullptr, &empty);
   if (rc != HGNN_OK || empty) return rc;
-  ScoreTopkBf16Args a{U, rows, n_rows, P, n_cand, L, topv, topi, x};
-  const int tc = st16_chunk(d, L, EXCL);
-  const size_t lds = st16_lds_bytes(d, L, tc);
-  const unsigned blocks = (unsigned)cdiv(n_rows, kSt16Users);
-  if (d == 64) launch_score_topk_bf16<64, EXCL>(tc, blocks, lds, stream, a);
-  else launch_score_topk_bf16<128, EXCL>(tc, blocks, lds, stream, a);
-  return check_launch("k_score_topk_bf16");
+  const ScoreTopkArgs a{U, rows, n_rows, P, n_cand, L, topv, topi, x};
+  const int tc = F::chunk(d, L, EXCL);
+  const size_t lds = st_lds_bytes<F>(d, L, tc);
+  const dim3 grid((unsigned)cdiv(n_rows, kStUsers));
+  if (d == 64) launch_score_topk<F, 64, EXCL>(tc, grid, lds, stream, a);
+  else launch_score_topk<F, 128, EXCL>(tc, grid, lds, stream, a);
+  return check_launch("k_score_topk");
 }
 
 // Metrics from the fused lists: one wave per row; rows where a tie crosses the cut get
@@ -851,35 +715,34 @@ int hgnn_topk_metrics(const float* scores, int64_t n_rows, int64_t n_cand, int64
 
 
 size_t hgnn_score_topk_lds_bytes(int32_t d, int32_t L) {
-  const int tc = 64, st = d + 8;
-  return (size_t)2 * tc * st * 4 + (size_t)kStWaves * kStUsersPerWave * L * 8;
+  return st_lds_bytes<StF32>(d, L, StF32::chunk(d, L, false));
 }
 
 int hgnn_score_topk(const float* U, const int32_t* rows, int64_t n_rows, const float* P,
                     int64_t n_cand, int32_t d, int32_t L, float* topv, int32_t* topi,
                     hgnn_stream_t stream) {
-  return score_topk_f32<false>("score_topk", U, rows, n_rows, P, n_cand, d, L, StExcl{}, topv,
-                               topi, as_stream(stream));
+  return score_topk<StF32, false>("score_topk", U, rows, n_rows, P, n_cand, d, L, StExcl{},
+                                  topv, topi, as_stream(stream));
 }
 
 int hgnn_score_topk_excl(const float* U, const int32_t* rows, int64_t n_rows, const float* P,
                          int64_t n_cand, int32_t d, int32_t L, const int32_t* excl_rowptr,
                          const int32_t* excl_col, const int32_t* excl_rows, float* topv,
                          int32_t* topi, hgnn_stream_t stream) {
-  return score_topk_f32<true>("score_topk_excl", U, rows, n_rows, P, n_cand, d, L,
-                              StExcl{excl_rowptr, excl_col, excl_rows}, topv, topi,
-                              as_stream(stream));
+  return score_topk<StF32, true>("score_topk_excl", U, rows, n_rows, P, n_cand, d, L,
+                                 StExcl{excl_rowptr, excl_col, excl_rows}, topv, topi,
+                                 as_stream(stream));
 }
 
 size_t hgnn_score_topk_bf16_lds_bytes(int32_t d, int32_t L) {
-  return st16_lds_bytes(d, L, st16_chunk(d, L, false));
+  return st_lds_bytes<StB16>(d, L, StB16::chunk(d, L, false));
 }
 
 int hgnn_score_topk_bf16(const uint16_t* U, const int32_t* rows, int64_t n_rows,
                          const uint16_t* P, int64_t n_cand, int32_t d, int32_t L, float* topv,
                          int32_t* topi, hgnn_stream_t stream) {
-  return score_topk_b16<false>("score_topk_bf16", U, rows, n_rows, P, n_cand, d, L, StExcl{},
-                               topv, topi, as_stream(stream));
+  return score_topk<StB16, false>("score_topk_bf16", U, rows, n_rows, P, n_cand, d, L, StExcl{},
+                                  topv, topi, as_stream(stream));
 }
 
 int hgnn_score_topk_excl_bf16(const uint16_t* U, const int32_t* rows, int64_t n_rows,
@@ -887,9 +750,9 @@ int hgnn_score_topk_excl_bf16(const uint16_t* U, const int32_t* rows, int64_t n_
                               const int32_t* excl_rowptr, const int32_t* excl_col,
                               const int32_t* excl_rows, float* topv, int32_t* topi,
                               hgnn_stream_t stream) {
-  return score_topk_b16<true>("score_topk_excl_bf16", U, rows, n_rows, P, n_cand, d, L,
-                              StExcl{excl_rowptr, excl_col, excl_rows}, topv, topi,
-                              as_stream(stream));
+  return score_topk<StB16, true>("score_topk_excl_bf16", U, rows, n_rows, P, n_cand, d, L,
+                                 StExcl{excl_rowptr, excl_col, excl_rows}, topv, topi,
+                                 as_stream(stream));
 }
 
 int hgnn_topk_finish(const float* topv, const int32_t* topi, int64_t n_rows, int32_t L,

@@ -84,6 +84,16 @@ def _fused_ok(d: int, fused: Optional[bool]) -> bool:
     return fused
 
 
+def _score_topk(U, rows, n, P, C, d, L, topv, topi, bf16, seen=None, excl_rows=None) -> None:
+    """The fused kernel, hgnn_score_topk[_excl][_bf16]: the top-L list of output row r, which
+    scores row ``rows[r]`` (or r) of U against P[:C], without the posts ``seen`` (a SeenIndex)
+    lists for user ``excl_rows[r]`` (or r)."""
+    entry = "hgnn_score_topk" + ("_excl" if seen is not None else "") + ("_bf16" if bf16 else "")
+    excl = () if seen is None else (N.ptr(seen.rowptr), N.ptr(seen._col), N.ptr(excl_rows))
+    N.check(getattr(N.lib(), entry)(N.ptr(U), N.ptr(rows), n, N.ptr(P), C, d, L, *excl,
+                                    N.ptr(topv), N.ptr(topi), N.stream_ptr(topv.device)), entry)
+
+
 def evaluate(test_edges: torch.Tensor, user_emb: torch.Tensor, post_emb: torch.Tensor,
              K: int = 10, num_users: Optional[int] = None,
              batch_scores: int = 1 << 30, fused: Optional[bool] = None,
@@ -129,14 +139,9 @@ def evaluate(test_edges: torch.Tensor, user_emb: torch.Tensor, post_emb: torch.T
         topi = torch.empty(n_rows, L, dtype=torch.int32, device=dev)
         tie = torch.empty(n_rows, dtype=torch.int32, device=dev)
         if bf16:
-            N.check(lib.hgnn_score_topk_bf16(N.ptr(U_b), None, n_rows, N.ptr(P_b), C, d, L,
-                                             N.ptr(topv), N.ptr(topi), N.stream_ptr(dev)),
-                    "hgnn_score_topk_bf16")
+            _score_topk(U_b, None, n_rows, P_b, C, d, L, topv, topi, True)
         else:
-            U = user_emb.contiguous()
-            N.check(lib.hgnn_score_topk(N.ptr(U), N.ptr(users32), n_rows, N.ptr(P_c), C, d, L,
-                                        N.ptr(topv), N.ptr(topi), N.stream_ptr(dev)),
-                    "hgnn_score_topk")
+            _score_topk(user_emb.contiguous(), users32, n_rows, P_c, C, d, L, topv, topi, False)
         N.check(lib.hgnn_topk_finish(N.ptr(topv), N.ptr(topi), n_rows, L, C, K, N.ptr(g.rowptr),
                                      N.ptr(g.true_cand), N.ptr(g.true_count), N.ptr(recall),
                                      N.ptr(ndcg), N.ptr(tie), N.stream_ptr(dev)),
@@ -243,80 +248,6 @@ def _mask_seen(S: torch.Tensor, seen: SeenIndex, ids: torch.Tensor) -> None:
     S[r, c] = -math.inf
 
 
-def _recommend_subset(user_emb, post_emb, K, batch_scores, fused, row_dtype, users, exclude):
-    """``recommend`` with ``users`` and / or ``exclude``."""
-    bf16 = _bf16_rows(user_emb, post_emb, row_dtype, "recommend")
-    seen = exclude if isinstance(exclude, SeenIndex) or exclude is None else None
-    dev = N.require_device(user_emb, post_emb, users, seen.rowptr if seen is not None else exclude)
-    n_u, C = int(user_emb.shape[0]), int(post_emb.shape[0])
-    if C == 0:
-        raise ValueError("recommend: no posts to rank")
-    if exclude is not None and seen is None:
-        seen = SeenIndex(exclude, n_u, C)
-    if seen is not None and (seen.num_users, seen.num_posts) != (n_u, C):
-        raise ValueError(f"recommend: exclude was built for {seen.num_users} users x "
-                         f"{seen.num_posts} posts, the tables hold {n_u} x {C}")
-    users32 = None if users is None else _check_users(users, n_u)
-    n = n_u if users is None else int(users32.numel())
-    k = min(K, C)
-    d = int(user_emb.shape[1])
-    out_s = torch.empty(n, k, dtype=torch.float32, device=dev)
-    out_i = torch.empty(n, k, dtype=torch.int32, device=dev)
-    if n == 0:
-        return out_s, out_i.long()
-    lib = N.lib()
-    cast = bf16 and user_emb.dtype != torch.bfloat16       # row_dtype="bf16" on fp32 tables
-    if cast:
-        # only the selected rows are cast: row r of U is users[r]'s
-        U = ops.rows_to_bf16(user_emb if users is None else user_emb.index_select(0, users32))
-        rows = None
-    else:
-        U, rows = user_emb.contiguous(), users32
-    P = _as_bf16(post_emb) if bf16 else post_emb.contiguous()
-    if _fused_ok(d, fused) and k <= 64:
-        entry = "hgnn_score_topk" + ("_excl" if seen is not None else "") + \
-            ("_bf16" if bf16 else "")
-        excl = () if seen is None else (N.ptr(seen.rowptr), N.ptr(seen._col), N.ptr(users32))
-        N.check(getattr(lib, entry)(N.ptr(U), N.ptr(rows), n, N.ptr(P), C, d, k, *excl,
-                                    N.ptr(out_s), N.ptr(out_i), N.stream_ptr(dev)), entry)
-        return out_s, out_i.long()
-    # materialised: the scores of a block of rows, -inf at the excluded posts, then the K best in
-    # rounds of up to 63 (hgnn_topk_metrics' list) with each round's winners set to -inf.  That
-    # kernel never lists a -inf score, and what it leaves in the slots past a row's last real
-    # entry is not an index to read with (INT_MAX, or a padding position of its scan): the slots
-    # that hold an entry are counted from the scores instead.
-    ld = (C + 4) // 4 * 4                                  # 16-B rows and a padding column
-    P_c = torch.zeros(ld, d, dtype=torch.float32, device=dev)
-    P_c[:C] = P.float()
-    nb = max(1, min(n, batch_scores // ld))
-    buf = torch.empty(nb, ld, dtype=torch.float32, device=dev)
-    no_rel = torch.zeros(nb + 1, dtype=torch.int32, device=dev)   # empty relevance sets
-    scratch = torch.empty(2, nb, dtype=torch.float64, device=dev)
-    for r0 in range(0, n, nb):
-        r1 = min(n, r0 + nb)
-        S = buf[: r1 - r0]
-        U_r = U[r0:r1] if rows is None else U.index_select(0, rows[r0:r1])
-        torch.mm(U_r.float(), P_c.T, out=S)
-        if seen is not None:
-            _mask_seen(S, seen, (torch.arange(r0, r1, device=dev) if users32 is None
-                                 else users32[r0:r1].long()))
-        for k0 in range(0, k, 63):
-            kr = min(63, k - k0)
-            idx = torch.empty(r1 - r0, kr, dtype=torch.int32, device=dev)
-            N.check(lib.hgnn_topk_metrics(
-                N.ptr(S), r1 - r0, C, ld, N.ptr(no_rel), N.ptr(no_rel), N.ptr(no_rel), kr,
-                N.ptr(idx), N.ptr(scratch[0]), N.ptr(scratch[1]), N.stream_ptr(dev)),
-                "hgnn_topk_metrics")
-            left = (S[:, :C] > -math.inf).sum(1, keepdim=True)   # candidates still unlisted
-            empty = torch.arange(kr, device=dev) >= left
-            at = torch.where(empty, ld - 1, idx).long()    # empty slots point at the padding
-            out_s[r0:r1, k0:k0 + kr] = S.gather(1, at).masked_fill_(empty, -math.inf)
-            out_i[r0:r1, k0:k0 + kr] = idx.masked_fill_(empty, -1)
-            if k0 + kr < k:
-                S.scatter_(1, at, -math.inf)
-    return out_s, out_i.long()
-
-
 def recommend(user_emb: torch.Tensor, post_emb: torch.Tensor, K: int = 10,
               batch_scores: int = 1 << 30, fused: Optional[bool] = None,
               row_dtype: str = _FP32, users: Optional[torch.Tensor] = None,
@@ -338,50 +269,77 @@ def recommend(user_emb: torch.Tensor, post_emb: torch.Tensor, K: int = 10,
     exclusion themselves (hgnn_score_topk_excl, hgnn_score_topk_excl_bf16); the materialised path
     writes -inf into the scores.  A user with fewer than k posts left gets score -inf and index
     -1 in the empty slots.  With ``row_dtype="bf16"`` on fp32 tables only the selected users'
-    rows are cast."""
-    if users is not None or exclude is not None:
-        return _recommend_subset(user_emb, post_emb, K, batch_scores, fused, row_dtype, users,
-                                 exclude)
+    rows are cast.
+
+    The materialised path ranks in rounds of 63 (hgnn_topk_metrics' list), so K > 63 there
+    returns the lists whether or not ``users`` / ``exclude`` are given."""
     bf16 = _bf16_rows(user_emb, post_emb, row_dtype, "recommend")
-    dev = N.require_device(user_emb, post_emb)
-    n, C = int(user_emb.shape[0]), int(post_emb.shape[0])
+    seen = exclude if isinstance(exclude, SeenIndex) or exclude is None else None
+    dev = N.require_device(user_emb, post_emb, users, seen.rowptr if seen is not None else exclude)
+    n_u, C = int(user_emb.shape[0]), int(post_emb.shape[0])
     if C == 0:
         raise ValueError("recommend: no posts to rank")
+    if exclude is not None and seen is None:
+        seen = SeenIndex(exclude, n_u, C)
+    if seen is not None and (seen.num_users, seen.num_posts) != (n_u, C):
+        raise ValueError(f"recommend: exclude was built for {seen.num_users} users x "
+                         f"{seen.num_posts} posts, the tables hold {n_u} x {C}")
+    users32 = None if users is None else _check_users(users, n_u)
+    n = n_u if users is None else int(users32.numel())
     k = min(K, C)
     d = int(user_emb.shape[1])
     out_s = torch.empty(n, k, dtype=torch.float32, device=dev)
     out_i = torch.empty(n, k, dtype=torch.int32, device=dev)
     if n == 0:
         return out_s, out_i.long()
-    lib = N.lib()
-    if bf16:
-        user_emb, post_emb = _as_bf16(user_emb), _as_bf16(post_emb)
+    if bf16 and user_emb.dtype != torch.bfloat16:          # row_dtype="bf16" on fp32 tables
+        # only the selected rows are cast: row r of U is users[r]'s
+        U = ops.rows_to_bf16(user_emb if users is None else user_emb.index_select(0, users32))
+        rows = None
+    else:
+        U, rows = user_emb.contiguous(), users32
+    P = _as_bf16(post_emb) if bf16 else post_emb.contiguous()
     if _fused_ok(d, fused) and k <= 64:
-        if bf16:
-            N.check(lib.hgnn_score_topk_bf16(N.ptr(user_emb), None, n, N.ptr(post_emb), C, d, k,
-                                             N.ptr(out_s), N.ptr(out_i), N.stream_ptr(dev)),
-                    "hgnn_score_topk_bf16")
-            return out_s, out_i.long()
-        N.check(lib.hgnn_score_topk(N.ptr(user_emb.contiguous()), None, n,
-                                    N.ptr(post_emb.contiguous()), C, d, k, N.ptr(out_s),
-                                    N.ptr(out_i), N.stream_ptr(dev)), "hgnn_score_topk")
+        _score_topk(U, rows, n, P, C, d, k, out_s, out_i, bf16, seen, users32)
         return out_s, out_i.long()
-    if bf16:
-        user_emb, post_emb = user_emb.float(), post_emb.float()   # R(U), R(P)
-    ld = (C + 3) // 4 * 4
-    P_c = post_emb.new_zeros(ld, d)
-    P_c[:C] = post_emb
-    rows = max(1, min(n, batch_scores // ld))
-    buf = torch.empty(rows, ld, dtype=torch.float32, device=dev)
-    no_rel = torch.zeros(rows + 1, dtype=torch.int32, device=dev)   # empty relevance sets
-    scratch = torch.empty(2, rows, dtype=torch.float64, device=dev)
-    for r0 in range(0, n, rows):
-        r1 = min(n, r0 + rows)
+    # materialised: the scores of a block of rows, -inf at the excluded posts, then the K best in
+    # rounds of up to 63 (hgnn_topk_metrics' list) with each round's winners set to -inf.  That
+    # kernel never lists a -inf score, and what it leaves in the slots past a row's last real
+    # entry is not an index to read with (INT_MAX, or a padding position of its scan): the slots
+    # that hold an entry are counted from the scores instead, and the empty ones point at a
+    # padding column of -inf.  Without exclusions no row ends short (k <= C) and none of that runs.
+    ld = (C + (3 if seen is None else 4)) // 4 * 4         # 16-B rows (and that padding column)
+    P_c = torch.zeros(ld, d, dtype=torch.float32, device=dev)
+    P_c[:C] = P.float()
+    nb = max(1, min(n, batch_scores // ld))
+    buf = torch.empty(nb, ld, dtype=torch.float32, device=dev)
+    no_rel = torch.zeros(nb + 1, dtype=torch.int32, device=dev)   # empty relevance sets
+    scratch = torch.empty(2, nb, dtype=torch.float64, device=dev)
+    lib = N.lib()
+    for r0 in range(0, n, nb):
+        r1 = min(n, r0 + nb)
         S = buf[: r1 - r0]
-        torch.mm(user_emb[r0:r1], P_c.T, out=S)
-        N.check(lib.hgnn_topk_metrics(
-            N.ptr(S), r1 - r0, C, ld, N.ptr(no_rel), N.ptr(no_rel), N.ptr(no_rel), K,
-            N.ptr(out_i[r0:r1]), N.ptr(scratch[0]), N.ptr(scratch[1]), N.stream_ptr(dev)),
-            "hgnn_topk_metrics")
-        out_s[r0:r1] = S.gather(1, out_i[r0:r1].long())
+        U_r = U[r0:r1] if rows is None else U.index_select(0, rows[r0:r1])
+        torch.mm(U_r.float(), P_c.T, out=S)
+        if seen is not None:
+            _mask_seen(S, seen, (torch.arange(r0, r1, device=dev) if users32 is None
+                                 else users32[r0:r1].long()))
+            S[:, C:] = -math.inf
+        for k0 in range(0, k, 63):
+            kr = min(63, k - k0)
+            idx = torch.empty(r1 - r0, kr, dtype=torch.int32, device=dev)
+            N.check(lib.hgnn_topk_metrics(
+                N.ptr(S), r1 - r0, C, ld, N.ptr(no_rel), N.ptr(no_rel), N.ptr(no_rel), kr,
+                N.ptr(idx), N.ptr(scratch[0]), N.ptr(scratch[1]), N.stream_ptr(dev)),
+                "hgnn_topk_metrics")
+            at = idx.long()
+            if seen is not None:
+                left = (S[:, :C] > -math.inf).sum(1, keepdim=True)   # candidates still unlisted
+                empty = torch.arange(kr, device=dev) >= left
+                at.masked_fill_(empty, ld - 1)
+                idx.masked_fill_(empty, -1)
+            out_s[r0:r1, k0:k0 + kr] = S.gather(1, at)
+            out_i[r0:r1, k0:k0 + kr] = idx
+            if k0 + kr < k:
+                S.scatter_(1, at, -math.inf)
     return out_s, out_i.long()
