@@ -526,6 +526,61 @@ int hgnn_score_gather2_zp(const void* xz, int64_t n_x, const float* rowvec, int3
                           int64_t n_chunks, int32_t chunk, float* slab, float* out,
                           hgnn_stream_t stream);
 
+/* ---- per-edge positive weights in the fused loss (opt-in: weighting="edge" in the Python layer) --
+ *   loss = mean_e( w_e * softplus(-<U[u_e],P[p_e]>) ) + mean_e softplus(<U[u_e],P[n_e]>)
+ * i.e. (pos_weights * BCEWithLogits(pos_scores, 1, reduction='none')).mean() + neg_loss: every
+ * positive edge's loss term and gradient carry that edge's own weight, where the entries above
+ * carry the one scalar c the reference's arithmetic collapses them to.  The gradient weight of
+ * positive edge e in dU and dP is c * w_e / E * (sigmoid(s_e) - 1) with c = *cscale, which stays a
+ * global factor (1 for the plain per-edge loss); the negatives are unchanged.  edge_w is an fp32
+ * device array over the positions of the grouping it sits beside (it follows that col array).
+ * Same lanes, same order of every sum, no atomics: with every weight one power of two, a result is
+ * bitwise the unweighted entry's with cscale scaled by it.  A null edge_w with rows to process is
+ * HGNN_E_ARG, before any launch. */
+
+/* The scoring pass with per-edge weights: edge_w[k] belongs to position k of rowptr_u / col_u (the
+ * user-grouped order).  The negatives in exactly one of the three forms (the other two NULL), dU,
+ * part, loss and err as hgnn_edge_score_fwd_bf16 has them; the optional per-position outputs are
+ * not produced.  fp32 rows: the widths of hgnn_edge_score_fwd (d <= 512). */
+int hgnn_edge_score_fwd_w(const float* U, const float* P, int32_t d, int64_t n_users,
+                          int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
+                          const float* edge_w, const int64_t* neg_i64, const int32_t* neg_i32,
+                          const uint64_t* d_seed, int64_t n_edges, const float* cscale, float* dU,
+                          float* part, float* loss, int32_t* err, hgnn_stream_t stream);
+/* ... with bf16 U and P (hgnn_edge_score_fwd_bf16's rule: d % 8 == 0 and d <= 512, else
+ * HGNN_E_UNSUPPORTED). */
+int hgnn_edge_score_fwd_w_bf16(const uint16_t* U, const uint16_t* P, int32_t d, int64_t n_users,
+                               int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
+                               const float* edge_w, const int64_t* neg_i64,
+                               const int32_t* neg_i32, const uint64_t* d_seed, int64_t n_edges,
+                               const float* cscale, float* dU, float* part, float* loss,
+                               int32_t* err, hgnn_stream_t stream);
+
+/* hgnn_score_gather2 with per-edge weights on the first list: edge_w[p] belongs to position p of
+ * rowptr / col (the post-grouped order; a heavy row's chunks read it at their absolute positions),
+ *   w_1(s) = c * inv_e * edge_w[p] * (sigmoid(s) - 1);
+ * the second list (the negatives, w_2) carries none and does not read edge_w.  The _zp and _bf16
+ * forms are hgnn_score_gather2_zp's and hgnn_score_gather2_bf16's, with their d rules; the _zp
+ * result is bitwise hgnn_score_gather2_w's on the unpacked table. */
+int hgnn_score_gather2_w(const float* x, int64_t n_x, const float* rowvec, int32_t d,
+                         const int32_t* rowptr, const int32_t* col, const float* edge_w,
+                         const int32_t* rowptr_n, const int32_t* col_n, int64_t n_rows,
+                         const float* cscale, float inv_e, const int32_t* heavy_rows,
+                         const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
+                         int32_t chunk, float* slab, float* out, hgnn_stream_t stream);
+int hgnn_score_gather2_w_zp(const void* xz, int64_t n_x, const float* rowvec, int32_t d,
+                            const int32_t* rowptr, const int32_t* col, const float* edge_w,
+                            const int32_t* rowptr_n, const int32_t* col_n, int64_t n_rows,
+                            const float* cscale, float inv_e, const int32_t* heavy_rows,
+                            const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
+                            int32_t chunk, float* slab, float* out, hgnn_stream_t stream);
+int hgnn_score_gather2_w_bf16(const uint16_t* x, int64_t n_x, const uint16_t* rowvec, int32_t d,
+                              const int32_t* rowptr, const int32_t* col, const float* edge_w,
+                              const int32_t* rowptr_n, const int32_t* col_n, int64_t n_rows,
+                              const float* cscale, float inv_e, const int32_t* heavy_rows,
+                              const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
+                              int32_t chunk, float* slab, float* out, hgnn_stream_t stream);
+
 /* ---- neighbour sampling for mini-batches (BASELINE cfg5; no reference counterpart) -----------
  * For each destination dst_ids[i] (rows of a destination-grouped CSR rowptr/col over n_rows):
  * keep all in-neighbours if deg <= fanout (or fanout < 0), else `fanout` distinct neighbour

@@ -160,6 +160,19 @@ _SIGS = {
                                        _p]),
     "hgnn_edge_score_fwd_bf16": (_c_i32, [_p, _p, _c_i32, _c_i64, _c_i64, _p, _p, _p, _p, _p,
                                           _c_i64, _p, _p, _p, _p, _p, _p]),
+    "hgnn_edge_score_fwd_w": (_c_i32, [_p, _p, _c_i32, _c_i64, _c_i64, _p, _p, _p, _p, _p, _p,
+                                       _c_i64, _p, _p, _p, _p, _p, _p]),
+    "hgnn_edge_score_fwd_w_bf16": (_c_i32, [_p, _p, _c_i32, _c_i64, _c_i64, _p, _p, _p, _p, _p,
+                                            _p, _c_i64, _p, _p, _p, _p, _p, _p]),
+    "hgnn_score_gather2_w": (_c_i32, [_p, _c_i64, _p, _c_i32, _p, _p, _p, _p, _p, _c_i64, _p,
+                                      ctypes.c_float, _p, _p, _c_i64, _c_i64, _c_i32, _p, _p,
+                                      _p]),
+    "hgnn_score_gather2_w_zp": (_c_i32, [_p, _c_i64, _p, _c_i32, _p, _p, _p, _p, _p, _c_i64, _p,
+                                         ctypes.c_float, _p, _p, _c_i64, _c_i64, _c_i32, _p, _p,
+                                         _p]),
+    "hgnn_score_gather2_w_bf16": (_c_i32, [_p, _c_i64, _p, _c_i32, _p, _p, _p, _p, _p, _c_i64,
+                                           _p, ctypes.c_float, _p, _p, _c_i64, _c_i64, _c_i32, _p,
+                                           _p, _p]),
     "hgnn_uniform_i32": (_c_i32, [_p, _c_i64, _c_i32, _p, _p]),
     "hgnn_scale_unless_one": (_c_i32, [_p, _c_i64, _p, _p]),
     "hgnn_linear_fwd_f32": (_c_i32, [_p, _c_i64, _c_i32, _p, _c_i32, _p, _p, _p]),

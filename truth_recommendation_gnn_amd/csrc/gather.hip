@@ -116,7 +116,12 @@ struct ZpMask {
 // offset is in the slot for any mask (zpack.h).  The masks of the next round (of the next
 // 64-edge batch after a batch's last round) are requested right after this round's values, so
 // the mask -> value dependency is exposed once per item, not once per round.
-template <int LPR, int UNROLL, bool NT>
+//
+// EW (the first list of hgnn_score_gather2_w_zp): the edge's weight edge_w[p] is loaded by the
+// lane that loads col[p], a batch ahead as cnext is (widx / wnext), and is shuffled to its slot
+// where the round's weights are formed, so no round holds a register per row for it; the order
+// of the mask and value loads is unchanged.
+template <int LPR, int UNROLL, bool NT, bool EW = false>
 __device__ __forceinline__ void segment_sum_zp(const GatherArgs& a, const int32_t* col, int score,
                                                int64_t beg, int64_t end, const float4& rv,
                                                float4& acc) {
@@ -131,6 +136,8 @@ __device__ __forceinline__ void segment_sum_zp(const GatherArgs& a, const int32_
   const char* xb = static_cast<const char*>(a.x);
   const int64_t S = zpack::slot_bytes(a.d);
   int cidx = lane < end - beg ? col[beg + lane] : 0;
+  float widx = 0.f;
+  if constexpr (EW) widx = lane < end - beg ? a.edge_w[beg + lane] : 0.f;
   uint32_t m[UNROLL];
   int src[UNROLL];
 #pragma unroll
@@ -142,6 +149,8 @@ __device__ __forceinline__ void segment_sum_zp(const GatherArgs& a, const int32_
     const int n = (int)min<int64_t>(64, end - base);
     const int64_t left = end - base - 64;   // edges of the batches after this one
     const int cnext = lane < left ? col[base + 64 + lane] : 0;
+    float wnext = 0.f;
+    if constexpr (EW) wnext = lane < left ? a.edge_w[base + 64 + lane] : 0.f;
     for (int j = 0; j < n; j += R) {
       uint4 t[UNROLL];
       uint32_t nib[UNROLL];
@@ -176,12 +185,16 @@ __device__ __forceinline__ void segment_sum_zp(const GatherArgs& a, const int32_
         sdot += V::dot(rv, v[u]);
         sdot = slot_sum<LPR>(sdot);
         const float sg = sigmoid_t(sdot, exp_neg_abs(sdot));
-        we[u] = cw * (score == 1 ? sg - 1.f : sg);
+        if constexpr (EW)   // (the weighted list is the positives': mode 1)
+          we[u] = cw * __shfl(widx, (j + u * NS + slot) & 63, 64) * (sg - 1.f);
+        else
+          we[u] = cw * (score == 1 ? sg - 1.f : sg);
       }
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) V::fma(acc, we[u], v[u]);
     }
     cidx = cnext;
+    if constexpr (EW) widx = wnext;
   }
 }
 
@@ -197,6 +210,10 @@ __device__ __forceinline__ void segment_sum_zp(const GatherArgs& a, const int32_
 // the bounds-predicated load of the plain kernel is (ISA: the UNROLL rows' loads, then one
 // s_waitcnt vmcnt(0), in both kernels).
 //
+// HAS_W with SC (the first list of hgnn_score_gather2_w): the recomputed weight is scaled by the
+// edge's own, w(s) = c * inv_e * edge_w[p] * (sigmoid(s) - 1), read at the absolute position p as
+// col is, so a heavy row's chunks need nothing new.
+//
 // XT: the source table's element type (RowSrc).  A bf16 row is read 16 B per lane, so d = 128 is
 // 16 lanes per row and 4 rows per wave load; its vectors stay packed while in flight and are
 // widened to fp32 where they are summed.  Everything after the load is fp32 either way.
@@ -209,9 +226,9 @@ __device__ __forceinline__ void segment_sum(const GatherArgs& a, const int32_t* 
   using V = Vec<W>;
   using S = RowSrc<XT, W>;
   if constexpr (ZP != 0) {
-    static_assert(SC && !HAS_W && !HOT && VPL == 1 && W == 4 && sizeof(XT) == 4,
+    static_assert(SC && !HOT && VPL == 1 && W == 4 && sizeof(XT) == 4,
                   "zero-packed rows: the fp32 score gather at d = 64 / 128");
-    segment_sum_zp<LPR, UNROLL, ZP == 2>(a, col, score, beg, end, rv[0], acc[0]);
+    segment_sum_zp<LPR, UNROLL, ZP == 2, HAS_W>(a, col, score, beg, end, rv[0], acc[0]);
     return;
   }
   constexpr int NS = 64 / LPR;
@@ -264,7 +281,8 @@ __device__ __forceinline__ void segment_sum(const GatherArgs& a, const int32_t* 
           for (int q = 0; q < VPL; ++q) sdot += V::dot(rv[q], S::widen(v[u][q]));
           sdot = slot_sum<LPR>(sdot);
           const float sg = sigmoid_t(sdot, exp_neg_abs(sdot));
-          we[u] = cw * (score == 1 ? sg - 1.f : sg);
+          if constexpr (HAS_W) we[u] = cw * we[u] * (sg - 1.f);   // (the positives: mode 1)
+          else we[u] = cw * (score == 1 ? sg - 1.f : sg);
         }
       }
 #pragma unroll
@@ -338,9 +356,10 @@ __device__ __forceinline__ void gather_item(const GatherArgs& a, const int64_t i
   if (own)
     segment_sum<LPR, VPL, W, UNROLL, HAS_W, SC, HOT, XT, ZP>(a, a.col, a.score, beg, end, rv,
                                                              acc);
+  // (the second list carries no per-edge weights: HAS_W stays off for it in a score gather)
   if (two && !partial)
-    segment_sum<LPR, VPL, W, UNROLL, HAS_W, SC, false, XT, ZP>(a, a.col2, 2, a.rowptr2[row],
-                                                               a.rowptr2[row + 1], rv, acc);
+    segment_sum<LPR, VPL, W, UNROLL, HAS_W && !SC, SC, false, XT, ZP>(
+        a, a.col2, 2, a.rowptr2[row], a.rowptr2[row + 1], rv, acc);
   slot_combine<LPR, VPL, W>(acc);
   if (!writer) return;
   float s = 1.f;
@@ -374,12 +393,12 @@ __global__ void __launch_bounds__(256) k_gather(const GatherArgs a) {
 // The ZP gather as its own kernel (ZP = 1, or 2 with nt value loads): it holds a round's loaded
 // words and the next round's masks at once, and left to itself the register allocator spent
 // 112 VGPRs on it (4 waves per SIMD); asked for 6 waves it fits without a spill in the loop.
-template <int LPR, int UNROLL, int ZP>
+template <int LPR, int UNROLL, int ZP, bool EW = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
 k_gather_zp(const GatherArgs a) {
   const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (item >= a.n_items) return;
-  gather_item<LPR, 1, 4, UNROLL, false, true, false, float, ZP>(a, item);
+  gather_item<LPR, 1, 4, UNROLL, EW, true, false, float, ZP>(a, item);
 }
 
 // Several gathers of one row width in one launch (hgnn_gather_reduce_multi): job j owns the
@@ -458,7 +477,7 @@ __global__ void __launch_bounds__(256) k_fixup(const GatherArgs a) {
 // ---------------------------------------------------------------------------------- host half
 // Every entry point is its own argument rules, gather_args (+ score_args / hot_args), run_gather;
 // run_gather validates, derives the Variant once and launches from the element type's width table.
-enum class Variant { kScore, kHotWeighted, kHot, kWeighted, kPlain };
+enum class Variant { kScore, kScoreWeighted, kHotWeighted, kHot, kWeighted, kPlain };
 
 // One row of a width table: the lane layout and the rows in flight per slot (the depth) per
 // variant: UM the mean / plain sum, UW weighted, US the score gather.
@@ -512,7 +531,7 @@ static int with_shape_bf16(int d, F&& f) {
   return f(Shape<64, 2, 8, 2, 2, 2>{});
 }
 
-// The five variants of one table row over XT rows (float, or uint16_t for bf16).
+// The six variants of one table row over XT rows (float, or uint16_t for bf16).
 template <typename XT, int LPR, int VPL, int W, int UM, int UW, int US>
 static int launch_gather(Shape<LPR, VPL, W, UM, UW, US>, const GatherArgs& a, Variant v,
                          hipStream_t stream) {
@@ -521,6 +540,7 @@ static int launch_gather(Shape<LPR, VPL, W, UM, UW, US>, const GatherArgs& a, Va
   hipLaunchKernelGGL((k_gather<LPR, VPL, W, U, HAS_W, SC, HOT, XT>), grid, block, 0, stream, a)
   switch (v) {
     case Variant::kScore: HGNN_G(US, false, true, false); break;
+    case Variant::kScoreWeighted: HGNN_G(US, true, true, false); break;   // per-edge weights
     // the two-policy loads as their own instantiations (hot_policy)
     case Variant::kHotWeighted: HGNN_G(UW, true, false, true); break;
     case Variant::kHot: HGNN_G(UM, false, false, true); break;
@@ -533,10 +553,15 @@ static int launch_gather(Shape<LPR, VPL, W, UM, UW, US>, const GatherArgs& a, Va
 
 // zero-packed source rows: the score gather's d = 64 / d = 128 forms (their lane layouts and
 // depths), nothing else (run_score2 alone sets GatherArgs::zp, after its width rule)
-static int launch_gather_zp(const GatherArgs& a, hipStream_t stream) {
+static int launch_gather_zp(const GatherArgs& a, Variant v, hipStream_t stream) {
   const dim3 grid((unsigned)cdiv(a.n_items, 4)), block(256);
-#define HGNN_GZP(LPR, ZP) \
-  hipLaunchKernelGGL((k_gather_zp<LPR, 4, ZP>), grid, block, 0, stream, a)
+#define HGNN_GZP(LPR, ZP)                                                                  \
+  do {                                                                                     \
+    if (v == Variant::kScoreWeighted)                                                      \
+      hipLaunchKernelGGL((k_gather_zp<LPR, 4, ZP, true>), grid, block, 0, stream, a);      \
+    else                                                                                   \
+      hipLaunchKernelGGL((k_gather_zp<LPR, 4, ZP>), grid, block, 0, stream, a);            \
+  } while (0)
   if (a.d == 64) {
     if (a.nt_load) HGNN_GZP(16, 2); else HGNN_GZP(16, 1);
   } else {
@@ -639,16 +664,18 @@ static int run_gather(GatherArgs a, int64_t n_x, hipStream_t stream) {
   if (a.n_heavy > 0 && (!a.heavy_rows || !a.heavy_first || !a.slab))
     return fail(HGNN_E_ARG, "gather: heavy rows without plan/slab");
   const bool has_w = a.edge_w || a.col_w;
-  if (a.score && (has_w || a.mean || !a.rowvec || (a.score == 1 && !a.cscale)))
+  // a score gather's only weights: edge_w on the positives (mode 1) of a two-list gather
+  const bool score_w = a.score == 1 && a.rowptr2 && a.edge_w && !a.col_w;
+  if (a.score && ((has_w && !score_w) || a.mean || !a.rowvec || (a.score == 1 && !a.cscale)))
     return fail(HGNN_E_ARG, "score_gather: bad mode/arguments");
   if (a.rowptr2 && a.score != 1)
     return fail(HGNN_E_ARG, "score_gather2: needs mode 1 for the first list");
-  const Variant v = a.score ? Variant::kScore
+  const Variant v = a.score ? (score_w ? Variant::kScoreWeighted : Variant::kScore)
                     : a.hot ? (has_w ? Variant::kHotWeighted : Variant::kHot)
                             : (has_w ? Variant::kWeighted : Variant::kPlain);
   int rc;
   if (a.zp)
-    rc = launch_gather_zp(a, stream);
+    rc = launch_gather_zp(a, v, stream);
   else if (a.bf16)
     rc = with_shape_bf16(a.d, [&](auto s) { return launch_gather<uint16_t>(s, a, v, stream); });
   else
@@ -665,19 +692,22 @@ static int run_gather(GatherArgs a, int64_t n_x, hipStream_t stream) {
 
 // The two-list score gathers: mode 1 over (rowptr, col) with the heavy-row plan, the negatives
 // (rowptr_n, col_n) in mode 2, one write per row; x holds fp32, bf16 or zero-packed fp32 rows.
+// `weighted`: the _w entries, whose positives carry edge_w (per position of rowptr / col).
 enum class Rows { kF32, kBf16, kZp };
 static int run_score2(const char* who, Rows rows, const void* x, int64_t n_x, const void* rowvec,
                       int32_t d, const int32_t* rowptr, const int32_t* col,
                       const int32_t* rowptr_n, const int32_t* col_n, int64_t n_rows,
                       const float* cscale, float inv_e, const int32_t* heavy_rows,
                       const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks, int32_t chunk,
-                      float* slab, float* out, hgnn_stream_t stream) {
+                      float* slab, float* out, hgnn_stream_t stream, bool weighted = false,
+                      const float* edge_w = nullptr) {
   if (rows == Rows::kBf16)
     if (int rc = bf16_width_rule(d, who)) return rc;
   if (rows == Rows::kZp && !zpack::width_ok(d))
     return fail(HGNN_E_UNSUPPORTED, "%s: d=%d (zero-packed rows: 64 or 128)", who, d);
   if (!rowptr_n && n_rows > 0) return fail(HGNN_E_ARG, "%s: rowptr_n is null", who);
-  GatherArgs a = gather_args(x, d, rowptr, col, n_rows, nullptr, nullptr, nullptr, 0, 0,
+  if (weighted && !edge_w && n_rows > 0) return fail(HGNN_E_ARG, "%s: edge_w is null", who);
+  GatherArgs a = gather_args(x, d, rowptr, col, n_rows, edge_w, nullptr, nullptr, 0, 0,
                              heavy_rows, heavy_first, n_heavy, n_chunks, chunk, slab, out);
   score_args(a, rowvec, cscale, inv_e, 1, rowptr_n, col_n);
   a.bf16 = rows == Rows::kBf16;
@@ -862,6 +892,39 @@ int hgnn_score_gather2_bf16(const uint16_t* x, int64_t n_x, const uint16_t* rowv
   return run_score2("score_gather2_bf16", Rows::kBf16, x, n_x, rowvec, d, rowptr, col, rowptr_n,
                     col_n, n_rows, cscale, inv_e, heavy_rows, heavy_first, n_heavy, n_chunks, chunk,
                     slab, out, stream);
+}
+
+int hgnn_score_gather2_w(const float* x, int64_t n_x, const float* rowvec, int32_t d,
+                         const int32_t* rowptr, const int32_t* col, const float* edge_w,
+                         const int32_t* rowptr_n, const int32_t* col_n, int64_t n_rows,
+                         const float* cscale, float inv_e, const int32_t* heavy_rows,
+                         const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
+                         int32_t chunk, float* slab, float* out, hgnn_stream_t stream) {
+  return run_score2("score_gather2_w", Rows::kF32, x, n_x, rowvec, d, rowptr, col, rowptr_n, col_n,
+                    n_rows, cscale, inv_e, heavy_rows, heavy_first, n_heavy, n_chunks, chunk, slab,
+                    out, stream, true, edge_w);
+}
+
+int hgnn_score_gather2_w_zp(const void* xz, int64_t n_x, const float* rowvec, int32_t d,
+                            const int32_t* rowptr, const int32_t* col, const float* edge_w,
+                            const int32_t* rowptr_n, const int32_t* col_n, int64_t n_rows,
+                            const float* cscale, float inv_e, const int32_t* heavy_rows,
+                            const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
+                            int32_t chunk, float* slab, float* out, hgnn_stream_t stream) {
+  return run_score2("score_gather2_w_zp", Rows::kZp, xz, n_x, rowvec, d, rowptr, col, rowptr_n,
+                    col_n, n_rows, cscale, inv_e, heavy_rows, heavy_first, n_heavy, n_chunks, chunk,
+                    slab, out, stream, true, edge_w);
+}
+
+int hgnn_score_gather2_w_bf16(const uint16_t* x, int64_t n_x, const uint16_t* rowvec, int32_t d,
+                              const int32_t* rowptr, const int32_t* col, const float* edge_w,
+                              const int32_t* rowptr_n, const int32_t* col_n, int64_t n_rows,
+                              const float* cscale, float inv_e, const int32_t* heavy_rows,
+                              const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
+                              int32_t chunk, float* slab, float* out, hgnn_stream_t stream) {
+  return run_score2("score_gather2_w_bf16", Rows::kBf16, x, n_x, rowvec, d, rowptr, col, rowptr_n,
+                    col_n, n_rows, cscale, inv_e, heavy_rows, heavy_first, n_heavy, n_chunks, chunk,
+                    slab, out, stream, true, edge_w);
 }
 
 }  // extern "C"

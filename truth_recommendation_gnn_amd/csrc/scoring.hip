@@ -1,15 +1,18 @@
 // Edge scoring + weighted BCE of the reference training step (train_gnn.py:259-281), fused.
 //
 //   s_pos[e] = <U[u_e], P[p_e]>,  s_neg[e] = <U[u_e], P[n_e]>
-//   loss = mean(pos_weights) * mean_e softplus(-s_pos) + mean_e softplus(s_neg)
+//   loss = mean(pos_weights) * mean_e softplus(-s_pos) + mean_e softplus(s_neg)      (default)
+//   loss = mean_e(w_e * softplus(-s_pos)) + mean_e softplus(s_neg)                   (per edge)
 //
-// (BCEWithLogitsLoss() reduces to a scalar, so the per-edge interaction weights collapse to their
-// mean — the reference's own arithmetic, reproduced.)
+// The default is the reference's own arithmetic, reproduced: BCEWithLogitsLoss() reduces to a
+// scalar, so its per-edge interaction weights collapse to their mean (the device scalar c).  The
+// per-edge mode (the EW instantiations, hgnn_edge_score_fwd_w) is the weighting that code meant:
+// each positive edge's loss term and gradient scaled by its own weight, read per position.
 //
 // Pass A (this file) walks the positive edges grouped by user (the CSC of the engages relation):
 // one wave per user keeps U[u] in registers, gathers P[p_e] and P[n_e] per edge, and in the same
 // pass produces the loss partials AND dL/dU for a unit upstream gradient
-//   dU[u] = sum_e  c/E (sigma(s_pos)-1) P[p_e] + 1/E sigma(s_neg) P[n_e]
+//   dU[u] = sum_e  c/E (sigma(s_pos)-1) P[p_e] + 1/E sigma(s_neg) P[n_e]      (per edge: c w_e/E)
 // with no atomics (the wave owns the row).  It also emits each edge's weights for dP:
 //   hpos (written at the edge's post-grouped position) and (n_e, u_e, hneg) for the negatives.
 // dP is then two K1-style weighted gathers of U rows (gather.hip): positives over the post-
@@ -50,6 +53,7 @@ struct ScoreArgs {
   float inv_e;
   int32_t d;
   int32_t nt_neg;              // nt policy: negatives' post rows loaded, dU rows stored
+  const float* edge_w;         // EW: weight of the positive edge per position (user-grouped order)
 };
 
 template <int LPR, int VPL, int W>
@@ -75,7 +79,10 @@ __device__ __forceinline__ float slot_dot(const typename Vec<W>::T (&a)[VPL],
 
 // XT: the element type of U and P (RowSrc).  bf16 rows are read 16 B per lane (W = 8), held packed
 // in the ping-pong sets and widened to fp32 where a step is scored; dU and the loss stay fp32.
-template <int LPR, int VPL, int W, bool NT = false, typename XT = float>
+// EW: per-edge positive weights.  The lane that loads col[base + lane] loads edge_w[base + lane]
+// with it (one more coalesced 256-B read per 64 edges) and the value reaches the scoring slot by
+// the shuffle pid takes; hp and the edge's loss term are scaled by it, nothing else moves.
+template <int LPR, int VPL, int W, bool NT = false, typename XT = float, bool EW = false>
 __global__ void __launch_bounds__(256) k_edge_score(const ScoreArgs a) {
   using V = Vec<W>;
   using S = RowSrc<XT, W>;
@@ -108,8 +115,10 @@ __global__ void __launch_bounds__(256) k_edge_score(const ScoreArgs a) {
     for (int64_t base = beg; base < end; base += 64) {
       const int n = (int)min<int64_t>(64, end - base);
       int pid = 0, nid = 0;
+      float pw = 0.f;
       if (lane < n) {
         pid = a.col[base + lane];
+        if constexpr (EW) pw = a.edge_w[base + lane];
         const int64_t nn = seed_p ? (int64_t)uniform_draw(seed, base + lane, (uint32_t)a.n_posts)
                            : a.neg32 ? (int64_t)a.neg32[base + lane] : a.neg[base + lane];
         if (nn < 0 || nn >= a.n_posts) {
@@ -153,11 +162,17 @@ __global__ void __launch_bounds__(256) k_edge_score(const ScoreArgs a) {
         const float tp = exp_neg_abs(sp), tn = exp_neg_abs(sn);
         float hp = c * a.inv_e * (sigmoid_t(sp, tp) - 1.f);
         float hn = a.inv_e * sigmoid_t(sn, tn);
+        float we = 1.f;
+        if constexpr (EW) {
+          we = __shfl(pw, e & 63, 64);
+          hp *= we;
+        }
         if (e >= n) hp = hn = 0.f;
         // loss terms once per edge, on the slot's first lane:
         //   softplus(-sp) = max(-sp, 0) + log(1 + t),  softplus(sn) = max(sn, 0) + log(1 + t)
         if (sl == 0 && e < n) {
-          lpos += fmaxf(-sp, 0.f) + __logf(1.f + tp);
+          if constexpr (EW) lpos += we * (fmaxf(-sp, 0.f) + __logf(1.f + tp));
+          else lpos += fmaxf(-sp, 0.f) + __logf(1.f + tp);
           lneg += fmaxf(sn, 0.f) + __logf(1.f + tn);
         }
 #pragma unroll
@@ -319,6 +334,15 @@ constexpr int64_t kLossOneMax = 65536;
 
 template <int LPR, int VPL, int W, typename XT = float>
 static int launch_score(const ScoreArgs& a, int64_t nblocks, hipStream_t stream) {
+  if (a.edge_w) {   // per-edge weights: their own instantiations too, under either policy
+    if (a.nt_neg)
+      hipLaunchKernelGGL((k_edge_score<LPR, VPL, W, true, XT, true>), dim3((unsigned)nblocks),
+                         dim3(256), 0, stream, a);
+    else
+      hipLaunchKernelGGL((k_edge_score<LPR, VPL, W, false, XT, true>), dim3((unsigned)nblocks),
+                         dim3(256), 0, stream, a);
+    return check_launch("k_edge_score");
+  }
   if (a.nt_neg)   // the cache policy as its own instantiation: the default one is unchanged
     hipLaunchKernelGGL((k_edge_score<LPR, VPL, W, true, XT>), dim3((unsigned)nblocks), dim3(256),
                        0, stream, a);
@@ -339,14 +363,16 @@ int64_t hgnn_edge_score_parts(int64_t n_users) {
   return (int64_t)align_up((size_t)(2 * cdiv(n_users, 4)), 4) + 4 * kRedBlocks;
 }
 
-// `bf16`: U and P hold bf16 rows (hgnn_edge_score_fwd_bf16)
+// `bf16`: U and P hold bf16 rows (hgnn_edge_score_fwd_bf16); `edge_w`: the per-edge weights of
+// the _w entries (null: the collapsed weighting, c alone)
 static int edge_score_fwd(const void* U, const void* P, int32_t d, int64_t n_users,
                           int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
                           const int64_t* neg_u_order, const int32_t* neg32,
                           const uint64_t* neg_seed, const int32_t* to_post_pos, int64_t n_edges, const float* cscale,
                           float* dU, float* hpos, int32_t* neg_key, int32_t* neg_user,
                           float* neg_w, float* part, float* loss, int32_t* err,
-                          hgnn_stream_t stream_, bool bf16 = false) {
+                          hgnn_stream_t stream_, bool bf16 = false,
+                          const float* edge_w = nullptr) {
   hipStream_t stream = as_stream(stream_);
   if (d < 1 || n_users < 0 || n_posts < 0 || n_edges < 0)
     return fail(HGNN_E_ARG, "edge_score: bad sizes");
@@ -357,7 +383,7 @@ static int edge_score_fwd(const void* U, const void* P, int32_t d, int64_t n_use
   if (err) (void)hipMemsetAsync(err, 0, sizeof(int32_t), stream);   // (null: not counted)
   ScoreArgs a{};
   a.U = U; a.P = P; a.rowptr = rowptr_u; a.col = col_u; a.neg = neg_u_order; a.neg32 = neg32;
-  a.neg_seed = neg_seed;
+  a.neg_seed = neg_seed; a.edge_w = edge_w;
   a.to_post_pos = to_post_pos; a.cscale = cscale; a.dU = dU; a.hpos = hpos; a.neg_key = neg_key;
   a.neg_u = neg_user; a.neg_w = neg_w; a.part = part; a.err = err; a.n_users = n_users;
   a.n_posts = n_posts; a.inv_e = n_edges > 0 ? 1.f / (float)n_edges : 0.f; a.d = d;
@@ -450,6 +476,51 @@ int hgnn_edge_score_fwd_bf16(const uint16_t* U, const uint16_t* P, int32_t d, in
   return edge_score_fwd(U, P, d, n_users, n_posts, rowptr_u, col_u, neg_i64, neg_i32, d_seed,
                         nullptr, n_edges, cscale, dU, nullptr, nullptr, nullptr, nullptr, part,
                         loss, err, stream, true);
+}
+
+// The per-edge entries: the argument rules of hgnn_edge_score_fwd_bf16 (`who` words them), then
+// the weights' own, all before any launch.
+static int edge_score_fwd_w(const char* who, bool bf16, const void* U, const void* P, int32_t d,
+                            int64_t n_users, int64_t n_posts, const int32_t* rowptr_u,
+                            const int32_t* col_u, const float* edge_w, const int64_t* neg_i64,
+                            const int32_t* neg_i32, const uint64_t* d_seed, int64_t n_edges,
+                            const float* cscale, float* dU, float* part, float* loss,
+                            int32_t* err, hgnn_stream_t stream) {
+  if (bf16 && d > 0 && (d % 8 != 0 || d > 512))
+    return fail(HGNN_E_UNSUPPORTED, "%s: d=%d (bf16 rows need d %% 8 == 0 and d <= 512)", who, d);
+  if (!bf16 && d > 512) return fail(HGNN_E_UNSUPPORTED, "edge_score: d=%d", d);
+  const int given = (neg_i64 != nullptr) + (neg_i32 != nullptr) + (d_seed != nullptr);
+  if (given > 1 || (n_edges > 0 && given != 1))
+    return fail(HGNN_E_ARG, "%s: the negatives come in exactly one form (int64, int32 or a seed)",
+                who);
+  if (d_seed && (n_posts < 1 || n_posts >= (int64_t(1) << 31) - 1))
+    return fail(HGNN_E_ARG, "%s: n_posts=%lld out of range for drawn negatives", who,
+                (long long)n_posts);
+  if (!edge_w && n_users > 0 && n_edges > 0) return fail(HGNN_E_ARG, "%s: edge_w is null", who);
+  return edge_score_fwd(U, P, d, n_users, n_posts, rowptr_u, col_u, neg_i64, neg_i32, d_seed,
+                        nullptr, n_edges, cscale, dU, nullptr, nullptr, nullptr, nullptr, part,
+                        loss, err, stream, bf16, edge_w);
+}
+
+int hgnn_edge_score_fwd_w(const float* U, const float* P, int32_t d, int64_t n_users,
+                          int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
+                          const float* edge_w, const int64_t* neg_i64, const int32_t* neg_i32,
+                          const uint64_t* d_seed, int64_t n_edges, const float* cscale, float* dU,
+                          float* part, float* loss, int32_t* err, hgnn_stream_t stream) {
+  return edge_score_fwd_w("edge_score_fwd_w", false, U, P, d, n_users, n_posts, rowptr_u, col_u,
+                          edge_w, neg_i64, neg_i32, d_seed, n_edges, cscale, dU, part, loss, err,
+                          stream);
+}
+
+int hgnn_edge_score_fwd_w_bf16(const uint16_t* U, const uint16_t* P, int32_t d, int64_t n_users,
+                               int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
+                               const float* edge_w, const int64_t* neg_i64,
+                               const int32_t* neg_i32, const uint64_t* d_seed, int64_t n_edges,
+                               const float* cscale, float* dU, float* part, float* loss,
+                               int32_t* err, hgnn_stream_t stream) {
+  return edge_score_fwd_w("edge_score_fwd_w_bf16", true, U, P, d, n_users, n_posts, rowptr_u,
+                          col_u, edge_w, neg_i64, neg_i32, d_seed, n_edges, cscale, dU, part,
+                          loss, err, stream);
 }
 
 // Uniform draws in [0, hi): out[i] = hi * (splitmix64(seed + i * golden) >> 32) >> 32 (Lemire's

@@ -588,25 +588,30 @@ def _score_gather(U, P, grouped, mode, cscale, inv_e, out, accumulate, tag):
             1 if accumulate else 0, N.stream_ptr(dev)), "hgnn_score_gather")
 
 
-def _score_gather2(U, P, pos, negs, cscale, inv_e, out, Uz=None):
+def _score_gather2(U, P, pos, negs, cscale, inv_e, out, Uz=None, edge_w=None):
     """Both dP gathers in one pass (hgnn_score_gather2): row r sums its positive edges (mode 1,
     heavy-row plan) and its negatives (mode 2) into one accumulator and writes dP[r] once.
     ``Uz``: ``zpack_rows(U)``; the gather then reads the packed rows (same sums, bit for bit;
-    the timer entry keeps its name and the unpacked table's algorithmic bytes)."""
+    the timer entry keeps its name and the unpacked table's algorithmic bytes).  ``edge_w``: the
+    positives' per-edge weights by position of ``pos`` (the ``_w`` entries; 4 B more per
+    positive edge)."""
     dev = out.device
     d = int(out.shape[1])
     n = pos.n_rows
     plan = _plan_args(pos.plan, d, dev)
     E = int(pos.col.numel()) + int(negs.col.numel())
     rb = _row_bytes(U)      # U's rows per edge and P's own row per output row
-    nb = gather_bytes(E, n, d, False, rb) + 4 * (n + 1) + n * rb
-    cb = gather_compulsory_bytes(E, n, int(U.shape[0]), d, False, rb) + 4 * (n + 1) + n * rb
+    wb = 4 * int(pos.col.numel()) if edge_w is not None else 0
+    nb = gather_bytes(E, n, d, False, rb) + 4 * (n + 1) + n * rb + wb
+    cb = gather_compulsory_bytes(E, n, int(U.shape[0]), d, False, rb) + 4 * (n + 1) + n * rb + wb
     # the entry point by the rows it reads: bf16, zero-packed fp32, fp32
-    entry, table = (("hgnn_score_gather2_bf16", U) if U.dtype == torch.bfloat16 else
-                    ("hgnn_score_gather2_zp", Uz) if Uz is not None else ("hgnn_score_gather2", U))
+    rows, table = (("_bf16", U) if U.dtype == torch.bfloat16 else
+                   ("_zp", Uz) if Uz is not None else ("", U))
+    entry = "hgnn_score_gather2" + ("_w" if edge_w is not None else "") + rows
+    weights = (N.ptr(edge_w),) if edge_w is not None else ()
     with _timed(f"score_gather[{n}<-{U.shape[0]}]x{d}", nb, cb):
         N.check(getattr(N.lib(), entry)(
-            N.ptr(table), U.shape[0], N.ptr(P), d, N.ptr(pos.rowptr), N.ptr(pos.col),
+            N.ptr(table), U.shape[0], N.ptr(P), d, N.ptr(pos.rowptr), N.ptr(pos.col), *weights,
             N.ptr(negs.rowptr), N.ptr(negs.col), n, N.ptr(cscale), inv_e, *plan, N.ptr(out),
             N.stream_ptr(dev)), entry)
 
@@ -1558,19 +1563,36 @@ def hetero_layer(spec: LayerSpec, x_dict: Dict[str, torch.Tensor],
 
 
 # ----------------------------------------------------------------------------- link loss
+WEIGHTINGS = ("mean", "edge")
+
+
+def _weighting_value(v: str, who: str) -> str:
+    if v not in WEIGHTINGS:
+        raise ValueError(f"{who}: weighting={v!r}; expected one of {WEIGHTINGS}")
+    return v
+
+
 def link_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: torch.Tensor,
-              neg_p: torch.Tensor, pos_weights: torch.Tensor) -> torch.Tensor:
+              neg_p: torch.Tensor, pos_weights: torch.Tensor,
+              weighting: str = "mean") -> torch.Tensor:
     """The reference training loss (train_gnn.py:259-281), on the device with torch ops.
 
-    ``BCEWithLogitsLoss()`` has mean reduction, so ``(pos_weights * pos_loss).mean()`` equals
-    ``mean(pos_weights) * pos_loss`` — reproduced as written."""
+    ``weighting="mean"``: ``BCEWithLogitsLoss()`` has mean reduction, so
+    ``(pos_weights * pos_loss).mean()`` equals ``mean(pos_weights) * pos_loss`` — reproduced as
+    written.  ``"edge"``: the positives' loss with ``reduction='none'``, so each positive edge's
+    term (and gradient) carries its own weight,
+    ``mean_e(w_e * softplus(-s_e)) + mean_e softplus(s_neg_e)``."""
+    _weighting_value(weighting, "link_loss")
     pos_u, pos_p = pos_edges[0], pos_edges[1]
     u = user_emb[pos_u]
     pos_scores = (u * post_emb[pos_p]).sum(dim=1)
     neg_scores = (u * post_emb[neg_p]).sum(dim=1)
     crit = torch.nn.functional.binary_cross_entropy_with_logits
-    pos_loss = crit(pos_scores, torch.ones_like(pos_scores))
     neg_loss = crit(neg_scores, torch.zeros_like(neg_scores))
+    if weighting == "edge":
+        pos_loss = crit(pos_scores, torch.ones_like(pos_scores), reduction="none")
+        return (pos_weights * pos_loss).mean() + neg_loss
+    pos_loss = crit(pos_scores, torch.ones_like(pos_scores))
     return (pos_weights * pos_loss).mean() + neg_loss
 
 
@@ -1585,6 +1607,53 @@ def _user_of_pos(csr: RelationCSR) -> torch.Tensor:
                                     deg).contiguous()
         csr._uop = m
     return m
+
+
+class EdgeWeights(NamedTuple):
+    """The positives' per-edge weights (``weighting="edge"``) in the orders the two loss kernels
+    walk: ``by_user[k]`` for position k of the user-grouped CSC (the scoring pass), ``by_post[p]``
+    for position p of the post-grouped CSR (the dP gather); fp32, and ``one``: the device scalar
+    1 that goes in as ``cscale``."""
+    by_user: torch.Tensor
+    by_post: torch.Tensor
+    one: torch.Tensor
+
+
+def edge_weights_in_kernel_order(csr: RelationCSR, pos_weights: torch.Tensor) -> EdgeWeights:
+    """``pos_weights`` ([E], COO order) permuted once per graph, as ``_user_of_pos`` is built once:
+    kept on the ``RelationCSR`` under the tensor's identity (held weakly and compared with ``is``:
+    an id could be reused) and its ``_version``, so the same weights cost no per-step permutation
+    and no host sync, and an in-place change rebuilds them.  2 x 4 B per edge."""
+    hit = getattr(csr, "_edge_w", None)
+    if hit is not None and hit[0]() is pos_weights and hit[1] == pos_weights._version:
+        return hit[2]
+    dev = N.require_device(pos_weights)
+    w = pos_weights.detach().to(torch.float32)
+
+    def ordered(perm):   # (a relation built from_csr: the positions are the edge ids)
+        return w.clone() if perm is None else w[perm.long()].contiguous()
+
+    ew = EdgeWeights(ordered(csr.bwd.perm), ordered(csr.fwd.perm),
+                     torch.ones((), dtype=torch.float32, device=dev))
+    csr._edge_w = (weakref.ref(pos_weights), pos_weights._version, ew)
+    return ew
+
+
+def _edge_weighting(who: str, weighting: str, pos_weights, n_edges: int, clashes) -> bool:
+    """The ``weighting`` argument of the two loss entry points checked (before anything touches
+    the device): whether it is "edge".  ``clashes``: {argument name: value} of the arguments
+    that "edge" does not combine with, each None when not given."""
+    if _weighting_value(weighting, who) == "mean":
+        return False
+    given = [k for k, v in clashes.items() if v is not None]
+    if given:
+        raise ValueError(f"{who}: weighting='edge' does not combine with {' / '.join(given)} "
+                         "(the sharded step keeps the scalar cscale; the per-edge loss takes "
+                         "its weights from pos_weights and its edge count from pos_edges)")
+    if pos_weights is None or tuple(pos_weights.shape) != (n_edges,):
+        raise ValueError(f"{who}: weighting='edge' needs pos_weights of shape [{n_edges}], one "
+                         "per positive edge in COO order")
+    return True
 
 
 def negatives_in_user_order(csr: RelationCSR, neg_p: torch.Tensor) -> torch.Tensor:
@@ -1703,7 +1772,7 @@ def presort_negatives(n_users: int, n_posts: int, pos_edges: torch.Tensor, neg_p
 
 
 def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total: int,
-              ready=None, on_dP=None, p_chunks=None, presorted=None):
+              ready=None, on_dP=None, p_chunks=None, presorted=None, edge_w=None):
     """Loss value and its gradients for a unit upstream gradient: (loss, dU, dP).  ``on_dP(dP)``,
     if given, is called once dP's kernels are enqueued and before the scoring pass (dU, the loss)
     is: the sharded step starts dP's reduce-scatter there, under the scoring pass.
@@ -1715,8 +1784,15 @@ def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total:
     ``U`` and ``P`` are fp32 tables, or both their bf16 copies (the bf16 row mode: both passes
     then read the bf16 rows, so the score <R(U[u]), R(P[p])> is one number in the scoring pass
     and in the dP gather; loss, dU and dP stay fp32).  The sharded step's arguments (``ready``,
-    ``on_dP``, ``p_chunks``) are for fp32 rows only."""
+    ``on_dP``, ``p_chunks``) are for fp32 rows only.
+
+    ``edge_w``: ``EdgeWeights`` (``weighting="edge"``), the positives' per-edge weights in the two
+    kernel orders; both passes then scale each positive edge by its own weight times ``cscale``.
+    Not with the sharded step's arguments."""
     sharded = ready is not None or on_dP is not None or p_chunks is not None
+    if edge_w is not None and sharded:
+        raise ValueError("edge_bce_loss: weighting='edge' does not combine with ready / on_dP / "
+                         "p_chunks (the sharded step keeps the scalar cscale)")
     U, P, relu_out = _loss_tables(U, P, csr, sharded)
     dev = N.require_device(U, P, neg_u_order)
     np_, E = P.shape[0], csr.num_edges
@@ -1734,12 +1810,14 @@ def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total:
     err = torch.empty(2, dtype=torch.int32, device=dev)
     c = cscale.to(torch.float32).reshape(()).contiguous()
     inv_e = 1.0 / n_total if n_total > 0 else 0.0
-    dP = _loss_dP(U, P, csr, negs, c, inv_e, err, relu_out, ready, p_chunks, presorted)
+    dP = _loss_dP(U, P, csr, negs, c, inv_e, err, relu_out, ready, p_chunks, presorted,
+                  edge_w.by_post if edge_w is not None else None)
     if on_dP is not None:
         on_dP(dP)
     if ready is not None and p_chunks is not None:
         ready()                                 # all of P, for the scoring pass
-    loss, dU = _loss_scoring_pass(U, P, csr, negs, c, n_total, err if check else None)
+    loss, dU = _loss_scoring_pass(U, P, csr, negs, c, n_total, err if check else None,
+                                  edge_w.by_user if edge_w is not None else None)
     if check and int(err[0]):
         raise ValueError("edge_bce_loss: negative post id out of range")
     return loss, dU, dP
@@ -1764,10 +1842,11 @@ def _loss_tables(U, P, csr: RelationCSR, sharded: bool):
 
 
 def _loss_dP(U, P, csr: RelationCSR, negs: _Negatives, c, inv_e, err, relu_out: bool, ready,
-             p_chunks, presorted) -> torch.Tensor:
+             p_chunks, presorted, edge_w=None) -> torch.Tensor:
     """The dP chain: sort the negatives (post, user) by post, then both dP gathers in one pass,
     each edge's weight recomputed from <U[u], P[post]> (hgnn_score_gather2); the scoring pass
-    (loss + dU) needs none of it.  ``ready`` / ``p_chunks``: see ``_edge_bce``."""
+    (loss + dU) needs none of it.  ``ready`` / ``p_chunks``: see ``_edge_bce``.  ``edge_w``: the
+    positives' weights in the post-grouped order (never with ``p_chunks``)."""
     from .graph import NO_SPLIT, GroupedEdges, Plan
     dev = U.device
     np_, E, pf = P.shape[0], csr.num_edges, csr.fwd
@@ -1797,12 +1876,15 @@ def _loss_dP(U, P, csr: RelationCSR, negs: _Negatives, c, inv_e, err, relu_out: 
     Uz = None
     if U.dtype != torch.bfloat16 and ready is None and zpack_on(U, relu_out):
         Uz = zpack_rows(U)
-    _score_gather2(U, P, pf, GroupedEdges(rowptr_n, nu_s, nu_s, no_plan, np_), c, inv_e, dP, Uz)
+    _score_gather2(U, P, pf, GroupedEdges(rowptr_n, nu_s, nu_s, no_plan, np_), c, inv_e, dP, Uz,
+                   edge_w)
     return dP
 
 
-def _loss_scoring_pass(U, P, csr: RelationCSR, negs: _Negatives, c, n_total: int, err):
-    """``(loss, dU)``; ``err``: where it counts out-of-range negatives, or None."""
+def _loss_scoring_pass(U, P, csr: RelationCSR, negs: _Negatives, c, n_total: int, err,
+                       edge_w=None):
+    """``(loss, dU)``; ``err``: where it counts out-of-range negatives, or None; ``edge_w``: the
+    positives' weights in the user-grouped order (the ``_w`` entries)."""
     # (The scoring pass takes no col_hot: with the positives' cold rows read nt it measured
     # 29-33 ms against 25.4 at cfg4 for every H tried, DESIGN §5.)
     dev = U.device
@@ -1814,8 +1896,16 @@ def _loss_scoring_pass(U, P, csr: RelationCSR, negs: _Negatives, c, n_total: int
     head = (N.ptr(U), N.ptr(P), d, nu, np_, N.ptr(ub.rowptr), N.ptr(ub.col))
     tail = (N.ptr(part), N.ptr(loss), N.ptr(err), s)
     rb = _row_bytes(U)     # per edge two post rows, per user its own row in and a dU row out
-    with _timed(f"edge_score_d{d}", E * (2 * rb + 12) + nu * (rb + 4 * d)):
-        if U.dtype == torch.bfloat16:
+    wb = 4 * E if edge_w is not None else 0
+    with _timed(f"edge_score_d{d}", E * (2 * rb + 12) + nu * (rb + 4 * d) + wb):
+        if edge_w is not None:
+            entry = ("hgnn_edge_score_fwd_w_bf16" if U.dtype == torch.bfloat16
+                     else "hgnn_edge_score_fwd_w")
+            N.check(getattr(lib, entry)(
+                *head, N.ptr(edge_w), N.ptr(negs.i64), N.ptr(negs.i32),
+                N.ptr(negs.draw.seed if negs.draw is not None else None), n_total, N.ptr(c),
+                N.ptr(dU), *tail), entry)
+        elif U.dtype == torch.bfloat16:
             N.check(lib.hgnn_edge_score_fwd_bf16(
                 *head, N.ptr(negs.i64), N.ptr(negs.i32),
                 N.ptr(negs.draw.seed if negs.draw is not None else None), n_total, N.ptr(c),
@@ -1848,16 +1938,18 @@ class _EdgeBCELoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total: int,
-                ready=None, presorted=None, bf16: bool = False):
+                ready=None, presorted=None, bf16: bool = False, edge_w=None):
         if bf16:
             # bf16 row mode: both passes read the bf16 copies, and those (half the bytes) are
             # what stays saved for the retained-graph recompute instead of U and P
             U, P = rows_to_bf16(U), rows_to_bf16(P)
         loss, dU, dP = _edge_bce(U, P, csr, neg_u_order, cscale, check, n_total, ready,
-                                 presorted=presorted)
+                                 presorted=presorted, edge_w=edge_w)
         ctx.grads = (dU, dP)
         ctx.save_for_backward(U, P)
-        ctx.args = (csr, neg_u_order, cscale, n_total)
+        # (edge_w: the weights as this forward read them, in kernel order; a later in-place
+        # change of the caller's tensor builds new ones and leaves these alone)
+        ctx.args = (csr, neg_u_order, cscale, n_total, edge_w)
         return loss
 
     @staticmethod
@@ -1865,8 +1957,8 @@ class _EdgeBCELoss(torch.autograd.Function):
     def backward(ctx, go):
         if ctx.grads is None:        # retained graph, second backward: recompute
             U, P = ctx.saved_tensors
-            csr, neg_u_order, cscale, n_total = ctx.args
-            _, dU, dP = _edge_bce(U, P, csr, neg_u_order, cscale, False, n_total)
+            csr, neg_u_order, cscale, n_total, edge_w = ctx.args
+            _, dU, dP = _edge_bce(U, P, csr, neg_u_order, cscale, False, n_total, edge_w=edge_w)
         else:
             dU, dP = ctx.grads
             ctx.grads = None         # handed on: autograd may accumulate into them from here
@@ -1876,7 +1968,7 @@ class _EdgeBCELoss(torch.autograd.Function):
             for t in (dU, dP):   # in place; a no-op launch for loss.backward()'s gradient of 1
                 N.check(lib.hgnn_scale_unless_one(N.ptr(t), t.numel(), N.ptr(g), s),
                         "hgnn_scale_unless_one")
-        return dU, dP, None, None, None, None, None, None, None, None
+        return dU, dP, None, None, None, None, None, None, None, None, None
 
 
 # A tensor carrying this attribute (set True) is a gradient of exactly 1 that nobody writes:
@@ -1899,8 +1991,17 @@ def edge_bce_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: tor
                   n_edges_total: Optional[int] = None,
                   cscale: Optional[torch.Tensor] = None, ready=None,
                   presorted: Optional["PresortedNegatives"] = None,
-                  row_dtype: Optional[str] = None) -> torch.Tensor:
+                  row_dtype: Optional[str] = None, weighting: str = "mean") -> torch.Tensor:
     """Fused HIP version of :func:`link_loss` (same value, same gradients).
+
+    ``weighting``: "mean" (the default) is the reference's arithmetic, the weights collapsed to
+    their mean; "edge" scales every positive edge's loss term and gradient by that edge's own
+    ``pos_weights[e]`` (:func:`link_loss`'s ``weighting="edge"``), inside the same two kernels:
+    ``pos_weights`` is then required with shape [E] in COO order, the kernels get ``cscale`` = 1,
+    and ``cscale``, ``n_edges_total`` and ``ready`` (the sharded step's arguments) are errors.
+    The weights are permuted to the kernels' orders once per graph and weights tensor
+    (:func:`edge_weights_in_kernel_order`).  It combines with ``presorted``, every form of
+    negatives, ``row_dtype="bf16"`` and ``HGNN_ZPACK``.
 
     ``neg_order='edge'``: ``neg_p[e]`` is the negative of COO edge e (the reference's layout);
     ``'user'``: already in the user-grouped order (what :func:`sample_negatives` draws).
@@ -1916,6 +2017,9 @@ def edge_bce_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: tor
     copies of the two tables (``_edge_bce``); the gradients pass straight through the rounding.
     A width that is no multiple of 8 keeps fp32 rows, and so does the sharded path (``ready``)
     under ``ROW_DTYPE`` — asking for "bf16" explicitly together with ``ready`` is an error."""
+    per_edge = _edge_weighting("edge_bce_loss", weighting, pos_weights, int(pos_edges.shape[1]),
+                               {"cscale": cscale, "n_edges_total": n_edges_total,
+                                "ready": ready})
     bf16 = resolve_row_dtype(row_dtype) == "bf16"
     if bf16 and ready is not None:
         if row_dtype is not None:
@@ -1927,7 +2031,10 @@ def edge_bce_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: tor
     if neg_p.shape[0] != csr.num_edges:
         raise ValueError("one negative per positive edge is required (train_gnn.py:272)")
     neg_u = _negatives_user_order(csr, neg_p, neg_order)
-    if cscale is None:
+    edge_w = edge_weights_in_kernel_order(csr, pos_weights) if per_edge else None
+    if per_edge:
+        cscale = edge_w.one
+    elif cscale is None:
         cscale = pos_weights.to(torch.float32).mean()
     n_total = csr.num_edges if n_edges_total is None else int(n_edges_total)
     if presorted is not None:
@@ -1936,19 +2043,32 @@ def edge_bce_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: tor
         _check_f32(user_emb, "edge_bce_loss user_emb")
         _check_f32(post_emb, "edge_bce_loss post_emb")
     return _EdgeBCELoss.apply(user_emb, post_emb, csr, neg_u, cscale, check, n_total, ready,
-                              presorted, bf16)
+                              presorted, bf16, edge_w)
 
 
 def edge_bce_loss_raw(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: torch.Tensor,
-                      neg_p: torch.Tensor, n_edges_total: int, cscale: torch.Tensor,
+                      neg_p: torch.Tensor, n_edges_total: Optional[int],
+                      cscale: Optional[torch.Tensor],
                       neg_order: str = "user", ready=None, on_dP=None, p_chunks=None,
-                      presorted: Optional[PresortedNegatives] = None, row_dtype: str = "fp32"):
+                      presorted: Optional[PresortedNegatives] = None, row_dtype: str = "fp32",
+                      pos_weights: Optional[torch.Tensor] = None, weighting: str = "mean"):
     """:func:`edge_bce_loss` outside autograd: (loss, dL/dU, dL/dP) from the same kernels, for
     callers that run their own backward schedule (``parallel.UserShard.step``; ``on_dP``,
     ``p_chunks``: see ``_edge_bce``; ``presorted``: from :func:`presort_negatives` on the same
     edges and draws).  ``row_dtype`` is "fp32" unless asked otherwise (never ``ROW_DTYPE``:
     the sharded step stays on fp32 rows); "bf16" casts the two tables and runs both passes on the
-    copies, and is an error together with ``p_chunks``, ``ready`` or ``on_dP``."""
+    copies, and is an error together with ``p_chunks``, ``ready`` or ``on_dP``.
+
+    ``weighting="edge"`` with ``pos_weights`` ([E], COO order): :func:`edge_bce_loss`'s per-edge
+    mode and its rules — ``n_edges_total`` and ``cscale`` are then passed as None (the edge count
+    is the positives', ``cscale`` is 1), and ``ready`` / ``on_dP`` / ``p_chunks`` are errors: the
+    sharded step keeps the scalar ``cscale``."""
+    per_edge = _edge_weighting("edge_bce_loss_raw", weighting, pos_weights,
+                               int(pos_edges.shape[1]),
+                               {"cscale": cscale, "n_edges_total": n_edges_total, "ready": ready,
+                                "on_dP": on_dP, "p_chunks": p_chunks})
+    if not per_edge and (cscale is None or n_edges_total is None):
+        raise ValueError("edge_bce_loss_raw: weighting='mean' needs n_edges_total and cscale")
     if _row_dtype_value(row_dtype, "row_dtype") == "bf16":
         if ready is not None or on_dP is not None or p_chunks is not None:
             raise ValueError("edge_bce_loss_raw: row_dtype='bf16' does not combine with "
@@ -1960,8 +2080,12 @@ def edge_bce_loss_raw(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges:
     neg_u = _negatives_user_order(csr, neg_p, neg_order)
     if presorted is not None:
         presorted.check_draws(neg_p, neg_order, "edge_bce_loss_raw")
+    edge_w = None
+    if per_edge:
+        edge_w = edge_weights_in_kernel_order(csr, pos_weights)
+        cscale, n_edges_total = edge_w.one, csr.num_edges
     return _edge_bce(user_emb, post_emb, csr, neg_u, cscale, False, int(n_edges_total), ready,
-                     on_dP, p_chunks, presorted)
+                     on_dP, p_chunks, presorted, edge_w)
 
 
 def _negatives_user_order(csr, neg_p, neg_order):
