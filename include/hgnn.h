@@ -581,6 +581,39 @@ int hgnn_score_gather2_w_bf16(const uint16_t* x, int64_t n_x, const uint16_t* ro
                               const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
                               int32_t chunk, float* slab, float* out, hgnn_stream_t stream);
 
+/* ---- n_neg negatives per positive edge in the scoring pass (opt-in: neg_p of shape [E, k]) -----
+ *   loss = <positive term> + 1/(E n_neg) sum_e sum_j softplus(<U[u_e],P[n_e,j]>)
+ * The negatives are row-major [E, n_neg] in the user-grouped order: negative j of position p of
+ * rowptr_u / col_u is element p * n_neg + j, in exactly one of the three forms (the other two
+ * NULL); drawn ones are uniform_draw(*d_seed, p * n_neg + j, n_posts), which is what
+ * hgnn_draw_sort_negatives and hgnn_uniform_i32 give for n = E * n_neg.
+ * Scaling convention: the kernel keeps the two factors of the entries above, c * inv_e on a
+ * positive edge and inv_e on a negative, so the caller passes
+ *   n_edges = (positive edges of the whole loss) * n_neg     and     *cscale = c * n_neg,
+ * which makes them c / E and 1 / (E n_neg); hgnn_score_gather2* takes the same pair
+ * (inv_e = 1 / n_edges) for dP, its second list holding all E * n_neg negatives.  The positions
+ * times n_neg must stay below 2^31 - 1 (the limit of the negatives sort; the caller's check).
+ * edge_w: per-edge positive weights as hgnn_edge_score_fwd_w has them, or NULL for the collapsed
+ * weighting.  One wave per user reads P[p_e] once and each P[n_e,j] once and writes dU[u] once, no
+ * atomics; two runs are bitwise equal.  An out-of-range negative is counted into err and
+ * contributes nothing.  The per-position outputs of hgnn_edge_score_fwd are not produced.
+ * n_neg < 1, more or fewer than one negative form, and n_posts out of range with a seed are
+ * HGNN_E_ARG; fp32 d > 512 is HGNN_E_UNSUPPORTED; all before any launch.  With n_neg = 1 the
+ * results are those of hgnn_edge_score_fwd_w (or, edge_w NULL, hgnn_edge_score_fwd*). */
+int hgnn_edge_score_fwd_k(const float* U, const float* P, int32_t d, int64_t n_users,
+                          int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
+                          const float* edge_w, const int64_t* neg_i64, const int32_t* neg_i32,
+                          const uint64_t* d_seed, int32_t n_neg, int64_t n_edges,
+                          const float* cscale, float* dU, float* part, float* loss, int32_t* err,
+                          hgnn_stream_t stream);
+/* ... with bf16 U and P (d % 8 == 0 and d <= 512, else HGNN_E_UNSUPPORTED). */
+int hgnn_edge_score_fwd_k_bf16(const uint16_t* U, const uint16_t* P, int32_t d, int64_t n_users,
+                               int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
+                               const float* edge_w, const int64_t* neg_i64,
+                               const int32_t* neg_i32, const uint64_t* d_seed, int32_t n_neg,
+                               int64_t n_edges, const float* cscale, float* dU, float* part,
+                               float* loss, int32_t* err, hgnn_stream_t stream);
+
 /* ---- neighbour sampling for mini-batches (BASELINE cfg5; no reference counterpart) -----------
  * For each destination dst_ids[i] (rows of a destination-grouped CSR rowptr/col over n_rows):
  * keep all in-neighbours if deg <= fanout (or fanout < 0), else `fanout` distinct neighbour

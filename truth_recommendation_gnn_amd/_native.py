@@ -164,6 +164,10 @@ _SIGS = {
                                        _c_i64, _p, _p, _p, _p, _p, _p]),
     "hgnn_edge_score_fwd_w_bf16": (_c_i32, [_p, _p, _c_i32, _c_i64, _c_i64, _p, _p, _p, _p, _p,
                                             _p, _c_i64, _p, _p, _p, _p, _p, _p]),
+    "hgnn_edge_score_fwd_k": (_c_i32, [_p, _p, _c_i32, _c_i64, _c_i64, _p, _p, _p, _p, _p, _p,
+                                       _c_i32, _c_i64, _p, _p, _p, _p, _p, _p]),
+    "hgnn_edge_score_fwd_k_bf16": (_c_i32, [_p, _p, _c_i32, _c_i64, _c_i64, _p, _p, _p, _p, _p,
+                                            _p, _c_i32, _c_i64, _p, _p, _p, _p, _p, _p]),
     "hgnn_score_gather2_w": (_c_i32, [_p, _c_i64, _p, _c_i32, _p, _p, _p, _p, _p, _c_i64, _p,
                                       ctypes.c_float, _p, _p, _c_i64, _c_i64, _c_i32, _p, _p,
                                       _p]),

@@ -237,6 +237,216 @@ __global__ void __launch_bounds__(256) k_edge_score(const ScoreArgs a) {
   }
 }
 
+// k negatives per positive edge (hgnn_edge_score_fwd_k): the arguments of k_edge_score and n_neg.
+// Its own struct and its own kernel, so the one-negative instantiations above are the same code
+// as before.  The negatives are row-major [E, n_neg] in the user-grouped order: negative j of
+// position p is element p * n_neg + j (drawn: uniform_draw(seed, p * n_neg + j, n_posts)).  The
+// caller folds the two means into the existing scales: inv_e = 1 / (E * n_neg) and
+// *cscale = c * n_neg, so a positive edge weighs c / E and a negative 1 / (E * n_neg).
+struct ScoreArgsK {
+  ScoreArgs s;
+  int32_t n_neg;
+};
+
+// One wave per user, U[u] in registers, as k_edge_score.  A 64-edge chunk is walked in sweeps of
+// the same two-set ping-pong: the first sweep is k_edge_score's two-row step (the positive row and
+// negative 0 of NS edges per step: with n_neg = 1 the same operations in the same order), then
+// every further pair of negative columns takes one sweep of two rows per edge, and an odd last
+// column a sweep of one.  So P[p_e] is read once and each P[n_e,j] once, all into the one dU
+// accumulator the wave owns.  A sweep's ids (lane = edge: neg[(base + lane) * n_neg + j], the
+// 64 * n_neg ids of a chunk being contiguous) are loaded before the previous sweep runs.  An
+// out-of-range id is counted into err and kept as -1: its row load reads post 0 and its weight
+// and loss term are zeroed.  hpos / neg_key / neg_w are not written.
+template <int LPR, int VPL, int W, bool NT = false, typename XT = float, bool EW = false>
+__global__ void __launch_bounds__(256) k_edge_score_k(const ScoreArgsK ak) {
+  using V = Vec<W>;
+  using S = RowSrc<XT, W>;
+  using Raw = typename S::Raw;
+  using Yes = std::true_type;
+  using No = std::false_type;
+  const ScoreArgs& a = ak.s;
+  const int K = ak.n_neg;
+  const XT* const Ux = static_cast<const XT*>(a.U);
+  const XT* const Px = static_cast<const XT*>(a.P);
+  constexpr int NS = 64 / LPR;
+  __shared__ float red[2][4];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int slot = lane / LPR, sl = lane % LPR;
+  const int64_t u = (int64_t)blockIdx.x * 4 + wave;
+  const float c = *a.cscale;
+  const int d = a.d;
+  const bool seed_p = a.neg_seed != nullptr;
+  const uint64_t seed = seed_p ? *a.neg_seed : 0;
+  float lpos = 0.f, lneg = 0.f;   // per-lane loss sums, on each slot's first lane
+  if (u < a.n_users) {
+    const int64_t beg = a.rowptr[u], end = a.rowptr[u + 1];
+    typename V::T uv[VPL], acc[VPL];
+#pragma unroll
+    for (int q = 0; q < VPL; ++q) {
+      const int cc = (q * LPR + sl) * W;
+      uv[q] = cc < d ? S::widen(S::load(Ux + u * d + cc)) : V::zero();
+      acc[q] = V::zero();
+    }
+    for (int64_t base = beg; base < end; base += 64) {
+      const int n = (int)min<int64_t>(64, end - base);
+      int pid = 0;
+      float pw = 0.f;
+      if (lane < n) {
+        pid = a.col[base + lane];
+        if constexpr (EW) pw = a.edge_w[base + lane];
+      }
+      // column j of this lane's edge as loaded (or drawn), checked only where its sweep starts:
+      // the check waits for the load, the load is issued a sweep ahead
+      auto raw_neg = [&](int j) -> int64_t {
+        if (lane >= n) return 0;
+        const int64_t i = (base + lane) * K + j;
+        return seed_p ? (int64_t)uniform_draw(seed, i, (uint32_t)a.n_posts)
+               : a.neg32 ? (int64_t)a.neg32[i] : a.neg[i];
+      };
+      auto checked = [&](int64_t nn) -> int {
+        if (nn < 0 || nn >= a.n_posts) {
+          if (a.err) atomicAdd(a.err, 1);
+          return -1;
+        }
+        return (int)nn;
+      };
+      // The steps of k_edge_score (its comment on the unconditional loads holds here), over the
+      // rows of one sweep: row 0 is the positive (pos0) or a negative, row 1 (two) a negative.
+      Raw a0[VPL], a1[VPL], b0[VPL], b1[VPL];
+      auto load_step = [&](auto pos0, auto two, int j, int id0, int id1, Raw (&x0)[VPL],
+                           Raw (&x1)[VPL]) {
+        const int e = j + slot;
+        const int r0 = max(__shfl(id0, e & 63, 64), 0);
+        int r1 = 0;
+        if constexpr (two) r1 = max(__shfl(id1, e & 63, 64), 0);
+#pragma unroll
+        for (int q = 0; q < VPL; ++q) {
+          const int cc = (q * LPR + sl) * W;
+          const int ccl = cc < d ? cc : 0;
+          if constexpr (NT && !pos0) x0[q] = S::load_nt(Px + (int64_t)r0 * d + ccl);
+          else x0[q] = S::load(Px + (int64_t)r0 * d + ccl);
+          if constexpr (two) {
+            if constexpr (NT) x1[q] = S::load_nt(Px + (int64_t)r1 * d + ccl);
+            else x1[q] = S::load(Px + (int64_t)r1 * d + ccl);
+          }
+        }
+      };
+      auto score_step = [&](auto pos0, auto two, int j, int id0, int id1, const Raw (&r0)[VPL],
+                            const Raw (&r1)[VPL]) {
+        const int e = j + slot;
+        typename V::T v0[VPL], v1[VPL];
+#pragma unroll
+        for (int q = 0; q < VPL; ++q) {
+          v0[q] = S::widen(r0[q]);
+          if constexpr (two) v1[q] = S::widen(r1[q]);
+        }
+        const float s0 = slot_dot<LPR, VPL, W>(uv, v0);
+        float s1 = 0.f;
+        if constexpr (two) s1 = slot_dot<LPR, VPL, W>(uv, v1);
+        const float t0 = exp_neg_abs(s0), t1 = exp_neg_abs(s1);
+        float h0, h1 = 0.f;
+        bool ok0 = e < n, ok1 = e < n;
+        if constexpr (pos0) {
+          h0 = c * a.inv_e * (sigmoid_t(s0, t0) - 1.f);
+        } else {
+          h0 = a.inv_e * sigmoid_t(s0, t0);
+          ok0 = ok0 && __shfl(id0, e & 63, 64) >= 0;
+        }
+        if constexpr (two) {
+          h1 = a.inv_e * sigmoid_t(s1, t1);
+          ok1 = ok1 && __shfl(id1, e & 63, 64) >= 0;
+        }
+        float we = 1.f;
+        if constexpr (EW && pos0) {
+          we = __shfl(pw, e & 63, 64);
+          h0 *= we;
+        }
+        if (!ok0) h0 = 0.f;
+        if (!ok1) h1 = 0.f;
+        // loss terms once per row, on the slot's first lane (k_edge_score's expressions)
+        if (sl == 0) {
+          if constexpr (pos0) {
+            if (ok0) {
+              // (a rounded product, then the add: what k_edge_score's expression compiles to,
+              // where this one would contract to an fma and differ in the loss's last bits)
+              const float sp0 = fmaxf(-s0, 0.f) + __logf(1.f + t0);
+              if constexpr (EW) {
+#pragma clang fp contract(off)
+                lpos += we * sp0;
+              } else {
+                lpos += sp0;
+              }
+            }
+          } else {
+            if (ok0) lneg += fmaxf(s0, 0.f) + __logf(1.f + t0);
+          }
+          if constexpr (two) {
+            if (ok1) lneg += fmaxf(s1, 0.f) + __logf(1.f + t1);
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < VPL; ++q) {
+          V::fma(acc[q], h0, v0[q]);
+          if constexpr (two) V::fma(acc[q], h1, v1[q]);
+        }
+      };
+      auto sweep = [&](auto pos0, auto two, int id0, int id1) {
+        load_step(pos0, two, 0, id0, id1, a0, a1);
+        for (int j = 0; j < n; j += 2 * NS) {
+          load_step(pos0, two, j + NS, id0, id1, b0, b1);
+          score_step(pos0, two, j, id0, id1, a0, a1);
+          if (j + NS >= n) break;
+          load_step(pos0, two, j + 2 * NS, id0, id1, a0, a1);
+          score_step(pos0, two, j + NS, id0, id1, b0, b1);
+        }
+      };
+      const int nid = checked(raw_neg(0));
+      int j = 1;
+      int64_t rw0 = 0, rw1 = 0;
+      if (j < K) rw0 = raw_neg(j);
+      if (j + 1 < K) rw1 = raw_neg(j + 1);
+      sweep(Yes{}, Yes{}, pid, nid);
+      while (j + 1 < K) {
+        const int i0 = checked(rw0), i1 = checked(rw1);
+        j += 2;
+        if (j < K) rw0 = raw_neg(j);
+        if (j + 1 < K) rw1 = raw_neg(j + 1);
+        sweep(No{}, Yes{}, i0, i1);
+      }
+      if (j < K) sweep(No{}, No{}, checked(rw0), 0);
+    }
+#pragma unroll
+    for (int m = LPR; m < 64; m <<= 1)
+#pragma unroll
+      for (int q = 0; q < VPL; ++q) V::add(acc[q], V::shfl_xor(acc[q], m));
+    if (lane < LPR) {
+#pragma unroll
+      for (int q = 0; q < VPL; ++q) {
+        const int cc = (q * LPR + sl) * W;
+        if (cc < d) {
+          if constexpr (NT) V::store_nt(a.dU + u * d + cc, acc[q]);
+          else V::store(a.dU + u * d + cc, acc[q]);
+        }
+      }
+    }
+  }
+  // deterministic block partials, as k_edge_score: wave tree, then waves in order
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    lpos += __shfl_xor(lpos, m, 64);
+    lneg += __shfl_xor(lneg, m, 64);
+  }
+  if (lane == 0) {
+    red[0][wave] = lpos;
+    red[1][wave] = lneg;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a.part[2 * blockIdx.x] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+    a.part[2 * blockIdx.x + 1] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+  }
+}
+
 // Deterministic two-level reduction of the block partials: 64 blocks each sum a contiguous
 // range (double), then one block sums the 64 and forms the loss.
 constexpr int kRedBlocks = 64;
@@ -332,8 +542,25 @@ __global__ void __launch_bounds__(1024) k_loss_one(const float* part, int64_t n_
 // few enough partials for one block to sum them faster than two launches
 constexpr int64_t kLossOneMax = 65536;
 
+template <int LPR, int VPL, int W, typename XT, bool NT, bool EW>
+static int launch_score_k(const ScoreArgs& a, int32_t n_neg, int64_t nblocks, hipStream_t stream) {
+  const ScoreArgsK ak{a, n_neg};
+  hipLaunchKernelGGL((k_edge_score_k<LPR, VPL, W, NT, XT, EW>), dim3((unsigned)nblocks),
+                     dim3(256), 0, stream, ak);
+  return check_launch("k_edge_score_k");
+}
+
+// n_neg > 0: the k-negative kernel (hgnn_edge_score_fwd_k), under the same two choices
 template <int LPR, int VPL, int W, typename XT = float>
-static int launch_score(const ScoreArgs& a, int64_t nblocks, hipStream_t stream) {
+static int launch_score(const ScoreArgs& a, int64_t nblocks, hipStream_t stream,
+                        int32_t n_neg = 0) {
+  if (n_neg > 0) {
+    if (a.edge_w)
+      return a.nt_neg ? launch_score_k<LPR, VPL, W, XT, true, true>(a, n_neg, nblocks, stream)
+                      : launch_score_k<LPR, VPL, W, XT, false, true>(a, n_neg, nblocks, stream);
+    return a.nt_neg ? launch_score_k<LPR, VPL, W, XT, true, false>(a, n_neg, nblocks, stream)
+                    : launch_score_k<LPR, VPL, W, XT, false, false>(a, n_neg, nblocks, stream);
+  }
   if (a.edge_w) {   // per-edge weights: their own instantiations too, under either policy
     if (a.nt_neg)
       hipLaunchKernelGGL((k_edge_score<LPR, VPL, W, true, XT, true>), dim3((unsigned)nblocks),
@@ -364,7 +591,7 @@ int64_t hgnn_edge_score_parts(int64_t n_users) {
 }
 
 // `bf16`: U and P hold bf16 rows (hgnn_edge_score_fwd_bf16); `edge_w`: the per-edge weights of
-// the _w entries (null: the collapsed weighting, c alone)
+// the _w entries (null: the collapsed weighting, c alone); `n_neg` > 0: the _k entries' kernel
 static int edge_score_fwd(const void* U, const void* P, int32_t d, int64_t n_users,
                           int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
                           const int64_t* neg_u_order, const int32_t* neg32,
@@ -372,7 +599,7 @@ static int edge_score_fwd(const void* U, const void* P, int32_t d, int64_t n_use
                           float* dU, float* hpos, int32_t* neg_key, int32_t* neg_user,
                           float* neg_w, float* part, float* loss, int32_t* err,
                           hgnn_stream_t stream_, bool bf16 = false,
-                          const float* edge_w = nullptr) {
+                          const float* edge_w = nullptr, int32_t n_neg = 0) {
   hipStream_t stream = as_stream(stream_);
   if (d < 1 || n_users < 0 || n_posts < 0 || n_edges < 0)
     return fail(HGNN_E_ARG, "edge_score: bad sizes");
@@ -395,16 +622,16 @@ static int edge_score_fwd(const void* U, const void* P, int32_t d, int64_t n_use
     // measured slower: users average ~20 edges, so wider steps waste the tail)
     if (bf16) {   // 16 B = 8 elements per lane: d = 128 is 16 lanes per row, 4 edges per step
       using B = uint16_t;
-      if (d <= 64) rc = launch_score<8, 1, 8, B>(a, nb, stream);
-      else if (d <= 128) rc = launch_score<16, 1, 8, B>(a, nb, stream);
-      else if (d <= 256) rc = launch_score<32, 1, 8, B>(a, nb, stream);
-      else rc = launch_score<64, 1, 8, B>(a, nb, stream);
+      if (d <= 64) rc = launch_score<8, 1, 8, B>(a, nb, stream, n_neg);
+      else if (d <= 128) rc = launch_score<16, 1, 8, B>(a, nb, stream, n_neg);
+      else if (d <= 256) rc = launch_score<32, 1, 8, B>(a, nb, stream, n_neg);
+      else rc = launch_score<64, 1, 8, B>(a, nb, stream, n_neg);
     }
-    else if (d % 4 == 0 && d <= 64) rc = launch_score<16, 1, 4>(a, nb, stream);
-    else if (d % 4 == 0 && d <= 128) rc = launch_score<32, 1, 4>(a, nb, stream);
-    else if (d % 4 == 0 && d <= 256) rc = launch_score<64, 1, 4>(a, nb, stream);
-    else if (d <= 64) rc = launch_score<64, 1, 1>(a, nb, stream);
-    else if (d <= 512) rc = launch_score<64, 8, 1>(a, nb, stream);
+    else if (d % 4 == 0 && d <= 64) rc = launch_score<16, 1, 4>(a, nb, stream, n_neg);
+    else if (d % 4 == 0 && d <= 128) rc = launch_score<32, 1, 4>(a, nb, stream, n_neg);
+    else if (d % 4 == 0 && d <= 256) rc = launch_score<64, 1, 4>(a, nb, stream, n_neg);
+    else if (d <= 64) rc = launch_score<64, 1, 1>(a, nb, stream, n_neg);
+    else if (d <= 512) rc = launch_score<64, 8, 1>(a, nb, stream, n_neg);
     else return fail(HGNN_E_UNSUPPORTED, "edge_score: d=%d", d);
     if (rc) return rc;
   }
@@ -521,6 +748,54 @@ int hgnn_edge_score_fwd_w_bf16(const uint16_t* U, const uint16_t* P, int32_t d, 
   return edge_score_fwd_w("edge_score_fwd_w_bf16", true, U, P, d, n_users, n_posts, rowptr_u,
                           col_u, edge_w, neg_i64, neg_i32, d_seed, n_edges, cscale, dU, part,
                           loss, err, stream);
+}
+
+// The k-negative entries: the argument rules of the _w entries under the entry's own name, with
+// edge_w optional, then n_neg's; all before any launch.
+static int edge_score_fwd_k(const char* who, bool bf16, const void* U, const void* P, int32_t d,
+                            int64_t n_users, int64_t n_posts, const int32_t* rowptr_u,
+                            const int32_t* col_u, const float* edge_w, const int64_t* neg_i64,
+                            const int32_t* neg_i32, const uint64_t* d_seed, int32_t n_neg,
+                            int64_t n_edges, const float* cscale, float* dU, float* part,
+                            float* loss, int32_t* err, hgnn_stream_t stream) {
+  if (n_neg < 1) return fail(HGNN_E_ARG, "%s: n_neg=%d (at least one negative per edge)", who,
+                             n_neg);
+  if (bf16 && d > 0 && (d % 8 != 0 || d > 512))
+    return fail(HGNN_E_UNSUPPORTED, "%s: d=%d (bf16 rows need d %% 8 == 0 and d <= 512)", who, d);
+  if (!bf16 && d > 512)
+    return fail(HGNN_E_UNSUPPORTED, "%s: d=%d (fp32 rows need d <= 512)", who, d);
+  const int given = (neg_i64 != nullptr) + (neg_i32 != nullptr) + (d_seed != nullptr);
+  if (given > 1 || (n_edges > 0 && given != 1))
+    return fail(HGNN_E_ARG, "%s: the negatives come in exactly one form (int64, int32 or a seed)",
+                who);
+  if (d_seed && (n_posts < 1 || n_posts >= (int64_t(1) << 31) - 1))
+    return fail(HGNN_E_ARG, "%s: n_posts=%lld out of range for drawn negatives", who,
+                (long long)n_posts);
+  return edge_score_fwd(U, P, d, n_users, n_posts, rowptr_u, col_u, neg_i64, neg_i32, d_seed,
+                        nullptr, n_edges, cscale, dU, nullptr, nullptr, nullptr, nullptr, part,
+                        loss, err, stream, bf16, edge_w, n_neg);
+}
+
+int hgnn_edge_score_fwd_k(const float* U, const float* P, int32_t d, int64_t n_users,
+                          int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
+                          const float* edge_w, const int64_t* neg_i64, const int32_t* neg_i32,
+                          const uint64_t* d_seed, int32_t n_neg, int64_t n_edges,
+                          const float* cscale, float* dU, float* part, float* loss, int32_t* err,
+                          hgnn_stream_t stream) {
+  return edge_score_fwd_k("edge_score_fwd_k", false, U, P, d, n_users, n_posts, rowptr_u, col_u,
+                          edge_w, neg_i64, neg_i32, d_seed, n_neg, n_edges, cscale, dU, part,
+                          loss, err, stream);
+}
+
+int hgnn_edge_score_fwd_k_bf16(const uint16_t* U, const uint16_t* P, int32_t d, int64_t n_users,
+                               int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
+                               const float* edge_w, const int64_t* neg_i64,
+                               const int32_t* neg_i32, const uint64_t* d_seed, int32_t n_neg,
+                               int64_t n_edges, const float* cscale, float* dU, float* part,
+                               float* loss, int32_t* err, hgnn_stream_t stream) {
+  return edge_score_fwd_k("edge_score_fwd_k_bf16", true, U, P, d, n_users, n_posts, rowptr_u,
+                          col_u, edge_w, neg_i64, neg_i32, d_seed, n_neg, n_edges, cscale, dU,
+                          part, loss, err, stream);
 }
 
 // Uniform draws in [0, hi): out[i] = hi * (splitmix64(seed + i * golden) >> 32) >> 32 (Lemire's

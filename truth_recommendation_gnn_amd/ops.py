@@ -1581,12 +1581,20 @@ def link_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: torch.T
     ``(pos_weights * pos_loss).mean()`` equals ``mean(pos_weights) * pos_loss`` — reproduced as
     written.  ``"edge"``: the positives' loss with ``reduction='none'``, so each positive edge's
     term (and gradient) carries its own weight,
-    ``mean_e(w_e * softplus(-s_e)) + mean_e softplus(s_neg_e)``."""
+    ``mean_e(w_e * softplus(-s_e)) + mean_e softplus(s_neg_e)``.
+
+    ``neg_p`` of shape ``[E, k]``: k negatives per positive edge, the same lines with a 2-D draw;
+    the negatives' term is then the mean over all E·k scores (``[E, 1]`` is ``[E]``)."""
     _weighting_value(weighting, "link_loss")
     pos_u, pos_p = pos_edges[0], pos_edges[1]
     u = user_emb[pos_u]
     pos_scores = (u * post_emb[pos_p]).sum(dim=1)
-    neg_scores = (u * post_emb[neg_p]).sum(dim=1)
+    if neg_p.dim() == 2 and neg_p.shape[1] == 1:
+        neg_p = neg_p.reshape(-1)
+    if neg_p.dim() == 2:
+        neg_scores = (u[:, None, :] * post_emb[neg_p]).sum(dim=-1)
+    else:
+        neg_scores = (u * post_emb[neg_p]).sum(dim=1)
     crit = torch.nn.functional.binary_cross_entropy_with_logits
     neg_loss = crit(neg_scores, torch.zeros_like(neg_scores))
     if weighting == "edge":
@@ -1684,25 +1692,65 @@ class _Negatives(NamedTuple):
     i64: Optional[torch.Tensor]
     i32: Optional[torch.Tensor]
     draw: Optional["NegativeDraw"]
+    k: int = 1      # negatives per positive edge: the tensors are row-major [E, k]
 
     @classmethod
     def of(cls, neg_u_order, E: int, n_posts: int) -> "_Negatives":
         """``neg_u_order`` checked against the ``E`` positive edges and ``n_posts``."""
+        k = _neg_count(neg_u_order, E, "edge_bce_loss")
         if isinstance(neg_u_order, NegativeDraw):
-            if neg_u_order.n != E or neg_u_order.num_posts != n_posts:
+            if neg_u_order.num_posts != n_posts:
                 raise ValueError("edge_bce_loss: the NegativeDraw does not match the positive "
                                  "edges")
-            return cls(None, None, neg_u_order)
-        if neg_u_order.numel() != E:
-            raise ValueError("edge_bce_loss: one negative per positive edge is required")
+            return cls(None, None, neg_u_order, k)
         if neg_u_order.dtype == torch.int32:
-            return cls(None, neg_u_order.contiguous(), None)
-        return cls(neg_u_order.to(torch.int64).contiguous(), None, None)
+            return cls(None, neg_u_order.contiguous(), None, k)
+        return cls(neg_u_order.to(torch.int64).contiguous(), None, None, k)
+
+
+def _neg_count(neg_p, E: int, who: str, sharded=None) -> int:
+    """k of negatives given as ``[E]`` / ``[E, k]`` (a tensor or a ``NegativeDraw``), checked
+    against the ``E`` positive edges before anything touches the device.  ``sharded``: {argument
+    name: value} of the sharded step's callbacks, which k >= 2 does not combine with."""
+    if isinstance(neg_p, NegativeDraw):
+        k = neg_p.num_neg
+        if neg_p.n != E * k:
+            raise ValueError(f"{who}: the NegativeDraw does not match the positive edges (it "
+                             f"draws {neg_p.n} = [{neg_p.n // k}, {k}] negatives; expected "
+                             f"[{E}, {k}] for {E} positive edges)")
+    else:
+        shape = tuple(neg_p.shape)
+        k = shape[1] if len(shape) == 2 else 1
+        if len(shape) not in (1, 2) or shape[0] != E or k < 1:
+            raise ValueError(f"{who}: neg_p of shape {list(shape)}; expected [{E}] (one negative "
+                             f"per positive edge) or [{E}, k] (k per positive edge)")
+    if E * k >= 2**31 - 1:
+        raise ValueError(f"{who}: {E} positive edges x {k} negatives reach the negatives sort's "
+                         "limit of 2^31 - 1 pairs")
+    given = [a for a, v in (sharded or {}).items() if v is not None]
+    if k >= 2 and given:
+        raise ValueError(f"{who}: {k} negatives per positive edge do not combine with "
+                         f"{' / '.join(given)} (the sharded step draws one negative per edge)")
+    return k
+
+
+def _user_of_draw(csr: RelationCSR, k: int) -> torch.Tensor:
+    """The sort's payload: the user of each of the E·k negatives (row-major [E, k], user-grouped
+    order).  k = 1 is ``_user_of_pos``; another k is built once per (graph, k) and kept on the
+    ``RelationCSR`` beside it, 4·E·k bytes."""
+    if k == 1:
+        return _user_of_pos(csr)
+    cache = csr.__dict__.setdefault("_uop_k", {})
+    m = cache.get(k)
+    if m is None:
+        m = cache[k] = _user_of_pos(csr).repeat_interleave(k).contiguous()
+    return m
 
 
 def _sort_negatives(negs: _Negatives, uop, E: int, np_: int, err, dev):
     """The negatives (user-grouped order) grouped by post: (rowptr over posts, users in that
-    order), stable — the order the dP gather sums them in."""
+    order), stable — the order the dP gather sums them in.  ``E``: the number of (post, user)
+    pairs, the positive edges times ``negs.k``; ``uop``: the user of each."""
     lib = N.lib()
     rowptr_n = torch.empty(np_ + 1, dtype=torch.int32, device=dev)
     nu_s = torch.empty(E, dtype=torch.int32, device=dev)
@@ -1739,21 +1787,30 @@ class PresortedNegatives:
     reused by a new object once the old one is freed), so a loss over other edges or other
     draws is refused."""
 
-    def __init__(self, csr, neg_p, neg_order: str, n_posts: int, rowptr, users):
+    def __init__(self, csr, neg_p, neg_order: str, n_posts: int, rowptr, users, k: int = 1):
         self.csr, self.neg_p, self.neg_order = csr, neg_p, neg_order
         self.n_posts = int(n_posts)
         self.rowptr, self.users = rowptr, users
+        self.k = int(k)            # negatives per positive edge the grouping holds
 
     def check_draws(self, neg_p, neg_order: str, where: str) -> None:
         if neg_order != self.neg_order:
             raise ValueError(f"{where}: presorted negatives were grouped with neg_order="
                              f"{self.neg_order!r}, the loss got neg_order={neg_order!r}")
+        k = (neg_p.num_neg if isinstance(neg_p, NegativeDraw)
+             else int(neg_p.shape[1]) if neg_p.dim() == 2 else 1)
+        if k != self.k:
+            raise ValueError(f"{where}: the presorted negatives hold {self.k} per positive edge, "
+                             f"the loss got {k}")
         if neg_p is not self.neg_p:
             raise ValueError(f"{where}: presorted negatives of other draws")
 
-    def check_edges(self, csr, n_posts: int) -> None:
+    def check_edges(self, csr, n_posts: int, k: int = 1) -> None:
         if csr is not self.csr or int(n_posts) != self.n_posts:
             raise ValueError("edge_bce_loss: the presorted negatives are for other edges")
+        if k != self.k:
+            raise ValueError(f"edge_bce_loss: the presorted negatives hold {self.k} per positive "
+                             f"edge, the loss got {k}")
 
 
 def presort_negatives(n_users: int, n_posts: int, pos_edges: torch.Tensor, neg_p,
@@ -1761,14 +1818,16 @@ def presort_negatives(n_users: int, n_posts: int, pos_edges: torch.Tensor, neg_p
     """The grouping ``edge_bce_loss_raw`` would sort its negatives into, done now (it needs
     only the edges and the draws, not the embeddings); pass it back as ``presorted=`` with the
     same ``neg_p`` and ``neg_order`` (required here: the two loss entry points default to
-    different orders)."""
+    different orders).  ``neg_p`` of shape ``[E, k]`` (or a ``NegativeDraw`` made for k): the
+    grouping of all E·k negatives, for a loss over the same k."""
+    k = _neg_count(neg_p, int(pos_edges.shape[1]), "presort_negatives")
     csr = relation_csr_for_loss(pos_edges, n_users, n_posts)
     E = csr.num_edges
     negs = _Negatives.of(_negatives_user_order(csr, neg_p, neg_order), E, n_posts)
     dev = csr.fwd.rowptr.device
     err = torch.zeros(2, dtype=torch.int32, device=dev)
-    rp, us = _sort_negatives(negs, _user_of_pos(csr), E, n_posts, err, dev)
-    return PresortedNegatives(csr, neg_p, neg_order, n_posts, rp, us)
+    rp, us = _sort_negatives(negs, _user_of_draw(csr, k), E * k, n_posts, err, dev)
+    return PresortedNegatives(csr, neg_p, neg_order, n_posts, rp, us, k)
 
 
 def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total: int,
@@ -1788,7 +1847,11 @@ def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total:
 
     ``edge_w``: ``EdgeWeights`` (``weighting="edge"``), the positives' per-edge weights in the two
     kernel orders; both passes then scale each positive edge by its own weight times ``cscale``.
-    Not with the sharded step's arguments."""
+    Not with the sharded step's arguments.
+
+    ``neg_u_order`` of shape ``[E, k]`` (or a ``NegativeDraw`` made for k): k negatives per
+    positive edge, row p those of user-grouped position p; ``n_total`` and ``cscale`` are given as
+    for one negative and scaled here.  Not with the sharded step's arguments either."""
     sharded = ready is not None or on_dP is not None or p_chunks is not None
     if edge_w is not None and sharded:
         raise ValueError("edge_bce_loss: weighting='edge' does not combine with ready / on_dP / "
@@ -1806,9 +1869,17 @@ def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total:
                 torch.zeros(U.shape, dtype=torch.float32, device=dev),
                 torch.zeros(P.shape, dtype=torch.float32, device=dev))
     negs = _Negatives.of(neg_u_order, E, np_)
+    if negs.k >= 2 and sharded:
+        raise ValueError(f"edge_bce_loss: {negs.k} negatives per positive edge do not combine "
+                         "with ready / on_dP / p_chunks (the sharded step draws one per edge)")
     # err[0]: zeroed and counted by the scoring pass, err[1] by the int64 negatives sort
     err = torch.empty(2, dtype=torch.int32, device=dev)
     c = cscale.to(torch.float32).reshape(()).contiguous()
+    if negs.k >= 2:
+        # The kernels weigh a positive edge c·inv_e and a negative inv_e.  With the edge count
+        # n_total·k and the device scalar c·k (one tiny multiply, no host sync) those are c/E and
+        # 1/(E·k): the mean over all E·k negatives, the positive term as with one negative.
+        n_total, c = n_total * negs.k, c * float(negs.k)
     inv_e = 1.0 / n_total if n_total > 0 else 0.0
     dP = _loss_dP(U, P, csr, negs, c, inv_e, err, relu_out, ready, p_chunks, presorted,
                   edge_w.by_post if edge_w is not None else None)
@@ -1852,10 +1923,11 @@ def _loss_dP(U, P, csr: RelationCSR, negs: _Negatives, c, inv_e, err, relu_out: 
     np_, E, pf = P.shape[0], csr.num_edges, csr.fwd
     dP = torch.empty(P.shape, dtype=torch.float32, device=dev)
     if presorted is not None:
-        presorted.check_edges(csr, np_)
+        presorted.check_edges(csr, np_, negs.k)
         rowptr_n, nu_s = presorted.rowptr, presorted.users
     else:
-        rowptr_n, nu_s = _sort_negatives(negs, _user_of_pos(csr), E, np_, err, dev)
+        rowptr_n, nu_s = _sort_negatives(negs, _user_of_draw(csr, negs.k), E * negs.k, np_, err,
+                                         dev)
     if ready is not None and p_chunks is None:
         # P is still arriving (parallel.py's all-gather of the post table): the sort above
         # needs only the edges, so it ran ahead; every kernel below reads P
@@ -1895,10 +1967,20 @@ def _loss_scoring_pass(U, P, csr: RelationCSR, negs: _Negatives, c, n_total: int
     loss = torch.empty((), dtype=torch.float32, device=dev)
     head = (N.ptr(U), N.ptr(P), d, nu, np_, N.ptr(ub.rowptr), N.ptr(ub.col))
     tail = (N.ptr(part), N.ptr(loss), N.ptr(err), s)
-    rb = _row_bytes(U)     # per edge two post rows, per user its own row in and a dU row out
+    # per positive edge 1 + k post rows and 4 + 8k index bytes (k = 1: two rows, 12 B), per user
+    # its own row in and a dU row out
+    rb, k = _row_bytes(U), negs.k
     wb = 4 * E if edge_w is not None else 0
-    with _timed(f"edge_score_d{d}", E * (2 * rb + 12) + nu * (rb + 4 * d) + wb):
-        if edge_w is not None:
+    with _timed(f"edge_score_d{d}", E * ((1 + k) * rb + 4 + 8 * k) + nu * (rb + 4 * d) + wb):
+        if k >= 2:
+            # (n_total and c come scaled by k from _edge_bce: hgnn.h's convention)
+            entry = ("hgnn_edge_score_fwd_k_bf16" if U.dtype == torch.bfloat16
+                     else "hgnn_edge_score_fwd_k")
+            N.check(getattr(lib, entry)(
+                *head, N.ptr(edge_w), N.ptr(negs.i64), N.ptr(negs.i32),
+                N.ptr(negs.draw.seed if negs.draw is not None else None), k, n_total, N.ptr(c),
+                N.ptr(dU), *tail), entry)
+        elif edge_w is not None:
             entry = ("hgnn_edge_score_fwd_w_bf16" if U.dtype == torch.bfloat16
                      else "hgnn_edge_score_fwd_w")
             N.check(getattr(lib, entry)(
@@ -2003,6 +2085,15 @@ def edge_bce_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: tor
     (:func:`edge_weights_in_kernel_order`).  It combines with ``presorted``, every form of
     negatives, ``row_dtype="bf16"`` and ``HGNN_ZPACK``.
 
+    ``neg_p`` of shape ``[E, k]`` (int64 or int32, or a ``NegativeDraw`` made with ``num_neg=k``):
+    k negatives per positive edge, :func:`link_loss`'s 2-D form — the negatives' term is the mean
+    over all E·k scores, the positive term is unchanged.  The scoring pass is then
+    ``hgnn_edge_score_fwd_k`` (each positive row read once, U[u] kept in registers), the sort and
+    the dP gather take the E·k (post, user) pairs.  ``[E]`` and ``[E, 1]`` are the one-negative
+    path, bit for bit.  k >= 2 combines with both weightings, ``row_dtype="bf16"``,
+    ``HGNN_ZPACK``, ``presorted``, ``check`` and ``n_edges_total`` / ``cscale``; with ``ready`` it
+    is an error (the sharded step draws one negative per edge).
+
     ``neg_order='edge'``: ``neg_p[e]`` is the negative of COO edge e (the reference's layout);
     ``'user'``: already in the user-grouped order (what :func:`sample_negatives` draws).
     ``check`` costs one host sync (the reference syncs every step with ``loss.item()``).
@@ -2020,6 +2111,7 @@ def edge_bce_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: tor
     per_edge = _edge_weighting("edge_bce_loss", weighting, pos_weights, int(pos_edges.shape[1]),
                                {"cscale": cscale, "n_edges_total": n_edges_total,
                                 "ready": ready})
+    _neg_count(neg_p, int(pos_edges.shape[1]), "edge_bce_loss", {"ready": ready})
     bf16 = resolve_row_dtype(row_dtype) == "bf16"
     if bf16 and ready is not None:
         if row_dtype is not None:
@@ -2062,11 +2154,17 @@ def edge_bce_loss_raw(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges:
     ``weighting="edge"`` with ``pos_weights`` ([E], COO order): :func:`edge_bce_loss`'s per-edge
     mode and its rules — ``n_edges_total`` and ``cscale`` are then passed as None (the edge count
     is the positives', ``cscale`` is 1), and ``ready`` / ``on_dP`` / ``p_chunks`` are errors: the
-    sharded step keeps the scalar ``cscale``."""
+    sharded step keeps the scalar ``cscale``.
+
+    ``neg_p`` of shape ``[E, k]``: :func:`edge_bce_loss`'s k negatives per positive edge
+    (``n_edges_total`` stays the number of positive edges); with k >= 2, ``ready`` / ``on_dP`` /
+    ``p_chunks`` are errors."""
     per_edge = _edge_weighting("edge_bce_loss_raw", weighting, pos_weights,
                                int(pos_edges.shape[1]),
                                {"cscale": cscale, "n_edges_total": n_edges_total, "ready": ready,
                                 "on_dP": on_dP, "p_chunks": p_chunks})
+    _neg_count(neg_p, int(pos_edges.shape[1]), "edge_bce_loss_raw",
+               {"ready": ready, "on_dP": on_dP, "p_chunks": p_chunks})
     if not per_edge and (cscale is None or n_edges_total is None):
         raise ValueError("edge_bce_loss_raw: weighting='mean' needs n_edges_total and cscale")
     if _row_dtype_value(row_dtype, "row_dtype") == "bf16":
@@ -2102,55 +2200,82 @@ def relation_csr_for_loss(pos_edges, n_users, n_posts) -> RelationCSR:
 
 
 class NegativeDraw:
-    """One uniform negative post per positive edge, not yet materialised: the device seed of a
-    counter-based draw (:func:`draw_negatives`).  The fused loss draws and groups them by post in
-    one call (``hgnn_draw_sort_negatives``: the draws are computed inside the sort's first pass,
-    not written by one kernel and read back by two); :meth:`tensor` gives the same int32 values
-    as :func:`sample_negatives` would for the same seed."""
+    """Uniform negative posts per positive edge (one, or ``num_neg``: row-major [E, num_neg], draw
+    p·num_neg + j being negative j of user-grouped position p), not yet materialised: the device
+    seed of a counter-based draw (:func:`draw_negatives`).  The fused loss draws and groups them by
+    post in one call (``hgnn_draw_sort_negatives``: the draws are computed inside the sort's first
+    pass, not written by one kernel and read back by two); :meth:`tensor` gives the same int32
+    values as :func:`sample_negatives` would for the same seed.  ``n``: the number of draws."""
 
-    def __init__(self, seed: torch.Tensor, n: int, num_posts: int):
+    def __init__(self, seed: torch.Tensor, n: int, num_posts: int, num_neg: int = 1):
         self.seed, self.n, self.num_posts = seed, int(n), int(num_posts)
-        self.shape = (self.n,)
+        self.num_neg = _num_neg_value(num_neg)
+        if self.n % self.num_neg:
+            raise ValueError(f"NegativeDraw: {self.n} draws are no multiple of num_neg={num_neg}")
+        self.shape = (self.n,) if self.num_neg == 1 else (self.n // self.num_neg, self.num_neg)
         self.dtype = torch.int32
         self.device = seed.device
 
     def tensor(self) -> torch.Tensor:
-        out = torch.empty(self.n, dtype=torch.int32, device=self.device)
+        out = torch.empty(self.shape, dtype=torch.int32, device=self.device)
         if self.n:
             N.check(N.lib().hgnn_uniform_i32(N.ptr(self.seed), self.n, self.num_posts, N.ptr(out),
                                              N.stream_ptr(self.device)), "hgnn_uniform_i32")
         return out
 
 
+def _num_neg_value(num_neg: int) -> int:
+    if int(num_neg) != num_neg or num_neg < 1:
+        raise ValueError(f"num_neg={num_neg!r}; expected a whole number of at least 1 negative "
+                         "per positive edge")
+    return int(num_neg)
+
+
+def _draw_count(E: int, num_neg: int) -> int:
+    if E * num_neg >= 2**31 - 1:
+        raise ValueError(f"{E} positive edges x num_neg={num_neg} reach the negatives sort's "
+                         "limit of 2^31 - 1 pairs")
+    return E * num_neg
+
+
 def draw_negatives(pos_edges: torch.Tensor, num_posts: int,
-                   generator: Optional[torch.Generator] = None) -> NegativeDraw:
+                   generator: Optional[torch.Generator] = None,
+                   num_neg: int = 1) -> NegativeDraw:
     """:func:`sample_negatives` without the materialised array: the seed only (one tiny device
-    draw from ``generator``, no host sync).  ``edge_bce_loss(..., neg_order='user')`` takes it."""
+    draw from ``generator``, no host sync).  ``edge_bce_loss(..., neg_order='user')`` takes it.
+    ``num_neg`` = k > 1: E·k draws, shape ``(E, k)``."""
+    num_neg = _num_neg_value(num_neg)
     dev = N.require_device(pos_edges)
     if num_posts < 1 or num_posts >= 2**31:
         raise ValueError(f"num_posts={num_posts} out of range")
+    n = _draw_count(int(pos_edges.shape[1]), num_neg)
     seed = torch.randint(0, 2**62, (1,), device=dev, dtype=torch.int64, generator=generator)
-    return NegativeDraw(seed, int(pos_edges.shape[1]), num_posts)
+    return NegativeDraw(seed, n, num_posts, num_neg)
 
 
 def sample_negatives(pos_edges: torch.Tensor, num_posts: int,
-                     generator: Optional[torch.Generator] = None) -> torch.Tensor:
+                     generator: Optional[torch.Generator] = None,
+                     num_neg: int = 1) -> torch.Tensor:
     """One uniform negative post per positive edge (train_gnn.py:272's ``torch.randint``), drawn
     directly in the user-grouped order: the draws are iid, so only their labels move.
+    ``num_neg`` = k > 1: k per positive edge, ``[E, k]`` (row p the negatives of user-grouped
+    position p); 1: ``[E]``.
 
     int32 draws from ``hgnn_uniform_i32`` (a counter-based generator seeded from ``generator``
     on the device, no host sync): in range by construction, so the loss sorts them without the
     int64 validation pass.  ``edge_bce_loss`` also takes int64 ``torch.randint`` negatives."""
+    num_neg = _num_neg_value(num_neg)
     dev = N.require_device(pos_edges)
     E = int(pos_edges.shape[1])
-    out = torch.empty(E, dtype=torch.int32, device=dev)
+    out = torch.empty(E if num_neg == 1 else (E, num_neg), dtype=torch.int32, device=dev)
     if E == 0:
         return out
     if num_posts < 1 or num_posts >= 2**31:
         raise ValueError(f"num_posts={num_posts} out of range")
+    n = _draw_count(E, num_neg)
     seed = torch.randint(0, 2**62, (1,), device=dev, dtype=torch.int64,
                          generator=generator)
-    N.check(N.lib().hgnn_uniform_i32(N.ptr(seed), E, int(num_posts), N.ptr(out),
+    N.check(N.lib().hgnn_uniform_i32(N.ptr(seed), n, int(num_posts), N.ptr(out),
                                      N.stream_ptr(dev)), "hgnn_uniform_i32")
     return out
 
