@@ -135,6 +135,14 @@ int hgnn_hot_cols(const int32_t* deg_rowptr, int64_t n_src, const int32_t* col, 
  * col_hot (tests).  No GPU needed.  The loss's scoring pass has no such path: measured, it lost
  * at every number of hot rows. */
 int32_t hgnn_hot_rows_policy(int64_t table_bytes, int32_t has_col_hot, float hot_share);
+/* The nt rule of a gather launch, as its launcher applies it.  `score` != 0 (the dP score
+ * gathers): the rows of a source table of n_x * d * elem_bytes >= 1 GiB are read with nt loads
+ * (elem_bytes: 4 for fp32 and zero-packed rows, which count by their unpacked size, 2 for bf16)
+ * and the output rows are then stored nt too.  `score` == 0 (K1 / K2, every job of
+ * hgnn_gather_reduce_multi): no nt loads; the fp32 output rows are stored nt where
+ * n_rows * d * 4 >= 1 GiB.  Sets *nt_load and *nt_store to 0 / 1.  No GPU needed. */
+int32_t hgnn_gather_nt_policy(int64_t n_x, int32_t d, int32_t elem_bytes, int32_t score,
+                              int64_t n_rows, int32_t* nt_load, int32_t* nt_store);
 
 /* ---- K1/K2: segmented gather-reduce over a CSR ----------------------------------------------
  *   out[i,:] (+)= s_i * sum_{p in [rowptr[i],rowptr[i+1])} w_p * x[col[p],:]
@@ -372,6 +380,14 @@ int hgnn_score_gather2(const float* x, int64_t n_x, const float* rowvec, int32_t
  * part needs hgnn_edge_score_parts(n_users) floats (16-B aligned); *err counts out-of-range negatives
  * (err nullable: not counted — a caller whose negatives are valid by construction). */
 int64_t hgnn_edge_score_parts(int64_t n_users);
+/* The two size rules of the scoring pass, as its launcher applies them (no GPU needed).
+ * hgnn_score_nt_policy: 1 where the post table, n_posts * d elements of 2 (bf16 != 0) or 4 bytes,
+ * has at least 256 MiB: the negatives' rows are then read with nt loads and the dU rows stored nt
+ * (the NT instantiations of every hgnn_edge_score_fwd* entry).  hgnn_loss_one_pass: 1 where the
+ * block partials (one per 4 users) are summed by one block, at most 65536 of them, i.e. up to
+ * 262144 users; 0 where two reduction kernels run. */
+int32_t hgnn_score_nt_policy(int64_t n_posts, int32_t d, int32_t bf16);
+int32_t hgnn_loss_one_pass(int64_t n_users);
 int hgnn_edge_score_fwd(const float* U, const float* P, int32_t d, int64_t n_users,
                         int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
                         const int64_t* neg_u_order, const int32_t* to_post_pos, int64_t n_edges,

@@ -41,6 +41,9 @@ _SIGS = {
     "hgnn_hot_cols_ws_bytes": (_c_sz, [_c_i64]),
     "hgnn_hot_cols": (_c_i32, [_p, _c_i64, _p, _c_i64, _c_i64, _p, _p, _p, _c_sz, _p]),
     "hgnn_hot_rows_policy": (_c_i32, [_c_i64, _c_i32, ctypes.c_float]),
+    "hgnn_gather_nt_policy": (_c_i32, [_c_i64, _c_i32, _c_i32, _c_i32, _c_i64, _p, _p]),
+    "hgnn_score_nt_policy": (_c_i32, [_c_i64, _c_i32, _c_i32]),
+    "hgnn_loss_one_pass": (_c_i32, [_c_i64]),
     "hgnn_gather_reduce_hot": (_c_i32, [_p, _c_i64, _c_i32, _p, _p, _c_i64, _p, _p, _c_i32, _p,
                                         _p, _c_i64, _c_i64, _c_i32, _p, _p, _c_i64, _p,
                                         ctypes.c_float, _p]),

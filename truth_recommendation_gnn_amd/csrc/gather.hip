@@ -575,11 +575,18 @@ static int launch_gather_zp(const GatherArgs& a, Variant v, hipStream_t stream) 
 // the dP gather / K2s / means are read by another kernel long after they left L2 (cfg4 step
 // 168.1 -> 167.5 ms with nt stores, mostly the dP gather); cfg2/cfg3 tables stay cache-resident.
 constexpr int64_t kNtBytes = int64_t(1) << 30;
+// The rule itself (hgnn_gather_nt_policy): a score gather streams the rows of a source table of
+// at least kNtBytes and then stores its rows nt too; any other gather stores nt where its output
+// is that large.
+static void gather_nt_policy(int64_t n_x, int32_t d, int64_t elem, bool score, int64_t n_rows,
+                             int32_t* nt_load, int32_t* nt_store) {
+  *nt_load = score && n_x * d * elem >= kNtBytes ? 1 : 0;
+  *nt_store = (score ? *nt_load != 0 : n_rows * d * 4 >= kNtBytes) ? 1 : 0;
+}
 // (`elem`: bytes per element of the source table, so the threshold sees the table's real size;
 // the output rows are fp32 either way)
 static void nt_policy(GatherArgs& a, int64_t n_x, int64_t elem = 4) {
-  a.nt_load = a.score && n_x * a.d * elem >= kNtBytes ? 1 : 0;
-  a.nt_store = (a.score ? a.nt_load : a.n_rows * a.d * 4 >= kNtBytes) ? 1 : 0;
+  gather_nt_policy(n_x, a.d, elem, a.score != 0, a.n_rows, &a.nt_load, &a.nt_store);
 }
 // (a zero-packed table counts by its unpacked size: the policy of hgnn_score_gather2)
 static int64_t elem_bytes(const GatherArgs& a) { return a.bf16 ? 2 : 4; }
@@ -733,6 +740,16 @@ int hgnn_gather_reduce(const float* x, int64_t n_x, int32_t d, const int32_t* ro
 
 int32_t hgnn_hot_rows_policy(int64_t table_bytes, int32_t has_col_hot, float hot_share) {
   return hot_policy(table_bytes, has_col_hot != 0, hot_share) ? 1 : 0;
+}
+
+int32_t hgnn_gather_nt_policy(int64_t n_x, int32_t d, int32_t elem_bytes, int32_t score,
+                              int64_t n_rows, int32_t* nt_load, int32_t* nt_store) {
+  if (d < 1 || n_x < 0 || n_rows < 0 || (elem_bytes != 2 && elem_bytes != 4) || !nt_load ||
+      !nt_store)
+    return fail(HGNN_E_ARG, "gather_nt_policy: n_x=%lld d=%d elem_bytes=%d n_rows=%lld",
+                (long long)n_x, d, elem_bytes, (long long)n_rows);
+  gather_nt_policy(n_x, d, elem_bytes, score != 0, n_rows, nt_load, nt_store);
+  return HGNN_OK;
 }
 
 int hgnn_gather_reduce_hot(const float* x, int64_t n_x, int32_t d, const int32_t* rowptr,

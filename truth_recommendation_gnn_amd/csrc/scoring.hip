@@ -541,6 +541,15 @@ __global__ void __launch_bounds__(1024) k_loss_one(const float* part, int64_t n_
 
 // few enough partials for one block to sum them faster than two launches
 constexpr int64_t kLossOneMax = 65536;
+// the rule by users (one partial per block of 4 user-waves): hgnn_loss_one_pass
+static bool loss_one_pass(int64_t n_users) { return cdiv(n_users, 4) <= kLossOneMax; }
+
+// The nt policy of the scoring pass (ScoreArgs::nt_neg, hgnn_score_nt_policy): on where the post
+// table, in the bytes of its stored dtype, outgrows the Infinity Cache.
+constexpr int64_t kScoreNtBytes = int64_t(256) << 20;
+static bool score_nt_policy(int64_t n_posts, int32_t d, bool bf16) {
+  return n_posts * d * (bf16 ? 2 : 4) >= kScoreNtBytes;
+}
 
 template <int LPR, int VPL, int W, typename XT, bool NT, bool EW>
 static int launch_score_k(const ScoreArgs& a, int32_t n_neg, int64_t nblocks, hipStream_t stream) {
@@ -590,6 +599,12 @@ int64_t hgnn_edge_score_parts(int64_t n_users) {
   return (int64_t)align_up((size_t)(2 * cdiv(n_users, 4)), 4) + 4 * kRedBlocks;
 }
 
+int32_t hgnn_score_nt_policy(int64_t n_posts, int32_t d, int32_t bf16) {
+  return score_nt_policy(n_posts, d, bf16 != 0) ? 1 : 0;
+}
+
+int32_t hgnn_loss_one_pass(int64_t n_users) { return loss_one_pass(n_users) ? 1 : 0; }
+
 // `bf16`: U and P hold bf16 rows (hgnn_edge_score_fwd_bf16); `edge_w`: the per-edge weights of
 // the _w entries (null: the collapsed weighting, c alone); `n_neg` > 0: the _k entries' kernel
 static int edge_score_fwd(const void* U, const void* P, int32_t d, int64_t n_users,
@@ -614,7 +629,7 @@ static int edge_score_fwd(const void* U, const void* P, int32_t d, int64_t n_use
   a.to_post_pos = to_post_pos; a.cscale = cscale; a.dU = dU; a.hpos = hpos; a.neg_key = neg_key;
   a.neg_u = neg_user; a.neg_w = neg_w; a.part = part; a.err = err; a.n_users = n_users;
   a.n_posts = n_posts; a.inv_e = n_edges > 0 ? 1.f / (float)n_edges : 0.f; a.d = d;
-  a.nt_neg = n_posts * d * (bf16 ? 2 : 4) >= (int64_t(256) << 20) ? 1 : 0;   // the table's bytes
+  a.nt_neg = score_nt_policy(n_posts, d, bf16) ? 1 : 0;
   const int64_t nb = cdiv(n_users, 4);   // blocks of 4 user-waves
   int rc = HGNN_OK;
   if (nb > 0) {
@@ -637,7 +652,7 @@ static int edge_score_fwd(const void* U, const void* P, int32_t d, int64_t n_use
   }
   // the reduction scratch lives after the block partials: part holds 2*nb floats + 2*64 doubles
   double* red = reinterpret_cast<double*>(part + align_up((size_t)(2 * nb), 4));
-  if (nb <= kLossOneMax) {
+  if (loss_one_pass(n_users)) {
     hipLaunchKernelGGL(k_loss_one, dim3(1), dim3(1024), 0, stream, part, nb, cscale, a.inv_e,
                        loss);
     return check_launch("k_loss_one");
