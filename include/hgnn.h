@@ -597,6 +597,69 @@ int hgnn_score_gather2_w_bf16(const uint16_t* x, int64_t n_x, const uint16_t* ro
                               const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
                               int32_t chunk, float* slab, float* out, hgnn_stream_t stream);
 
+/* ---- popularity-weighted negatives (opt-in) ---------------------------------------------------
+ * The table of a discrete distribution over the posts and the draws from it.
+ *   q[n_posts]        int64 weights, each in [0, 2^32), their sum T in [1, 2^63)
+ *   cdf[n_posts + 1]  the exclusive cumulative sums, cdf[n_posts] = T (hgnn_weighted_cdf_build;
+ *                     integers, so exact and independent of the summation order)
+ *   draw c            x = splitmix64(*d_seed + c * golden), the word hgnn_uniform_i32 forms before
+ *                     its shift; r = (x * T) >> 64, the high half of the 64 x 64-bit product; the
+ *                     draw is the unique post j with cdf[j] <= r < cdf[j + 1].
+ * A post of weight 0 is never drawn.  The search runs between two entries of a guide table
+ * (hgnn_weighted_guide_build): guide[b], b in [0, n_guide], is the post holding b << shift (the last
+ * post where that is T or more); the caller chooses shift and n_guide with
+ * (T - 1) >> shift < n_guide.  The caller reads T = cdf[n_posts] once per distribution.
+ * Workspace of the cdf: hgnn_weighted_cdf_ws_bytes(n_posts). */
+size_t hgnn_weighted_cdf_ws_bytes(int64_t n_posts);
+int hgnn_weighted_cdf_build(const int64_t* q, int64_t n_posts, int64_t* cdf, void* ws,
+                            size_t ws_bytes, hgnn_stream_t stream);
+int hgnn_weighted_guide_build(const int64_t* cdf, int64_t n_posts, int64_t T, int32_t shift,
+                              int32_t n_guide, int32_t* guide, hgnn_stream_t stream);
+/* out[c] = draw c for c in [0, n); the seed is read from device memory (no host sync). */
+int hgnn_weighted_i32(const uint64_t* d_seed, int64_t n, const int64_t* cdf, int64_t n_posts,
+                      int64_t T, const int32_t* guide, int32_t shift, int32_t n_guide,
+                      int32_t* out, hgnn_stream_t stream);
+/* Draws that avoid the posts a user has seen.  Draw i = p * n_neg + j belongs to user-grouped
+ * position p, whose user is user_of_pos[p]; attempt t = 0 .. tries - 1 is draw i + t * n above, so
+ * attempt 0 is hgnn_weighted_i32's.  The first attempt not in the user's seen list (seen_rowptr
+ * [n_users + 1] / seen_col, ascending per user) is kept; if all are seen the last is kept and
+ * *d_kept_seen (device int64, nullable, never zeroed here) is incremented.  cdf == NULL: the
+ * uniform distribution, attempt t being hgnn_uniform_i32's draw at that counter (guide, T unused). */
+int hgnn_weighted_avoid_i32(const uint64_t* d_seed, int64_t n, int32_t n_neg, const int64_t* cdf,
+                            int64_t n_posts, int64_t T, const int32_t* guide, int32_t shift,
+                            int32_t n_guide, const int32_t* user_of_pos, int64_t n_users,
+                            const int32_t* seen_rowptr, const int32_t* seen_col, int32_t tries,
+                            int32_t* out, int64_t* d_kept_seen, hgnn_stream_t stream);
+
+/* The degree-skew plan made on the device with nothing read back: hgnn_plan_fill into arrays
+ * sized by a bound (heavy_rows[max_heavy], heavy_first[max_heavy + 1]) and the two counts
+ * {n_heavy, n_chunks} left in d_counts2 (device int32[2]).  For lists of n_pairs entries in all,
+ * max_heavy = n_pairs / chunk bounds the heavy rows and 2 * max_heavy the chunks.
+ * Workspace: hgnn_plan_ws_bytes(n_rows). */
+int hgnn_plan_device(const int32_t* rowptr, int64_t n_rows, int32_t chunk, int64_t max_heavy,
+                     int32_t* heavy_rows, int32_t* heavy_first, int32_t* d_counts2, void* ws,
+                     size_t ws_bytes, hgnn_stream_t stream);
+
+/* hgnn_score_gather2 for negatives whose lists are skewed (drawn by popularity): the negatives'
+ * lists longer than `chunk` are summed chunk by chunk into neg_slab (2 * neg_max_heavy rows of d
+ * floats), one wave per chunk, by the plan hgnn_plan_device made from rowptr_n with the same
+ * chunk; a fix-up in fixed order then adds the positives' partial sums and the negatives' to the
+ * row, so two runs are bitwise equal.  The grid is sized by neg_max_heavy; waves beyond the
+ * device-side counts return at once.  rows: the format of x and rowvec (HGNN_ROWS_*; zero-packed:
+ * x packed, rowvec fp32); edge_w: the positives' per-edge weights or NULL. */
+#define HGNN_ROWS_F32 0
+#define HGNN_ROWS_BF16 1
+#define HGNN_ROWS_ZP 2
+int hgnn_score_gather2_planned(int32_t rows, const void* x, int64_t n_x, const void* rowvec,
+                               int32_t d, const int32_t* rowptr, const int32_t* col,
+                               const float* edge_w, const int32_t* rowptr_n, const int32_t* col_n,
+                               int64_t n_rows, const float* cscale, float inv_e,
+                               const int32_t* heavy_rows, const int32_t* heavy_first,
+                               int64_t n_heavy, int64_t n_chunks, int32_t chunk, float* slab,
+                               const int32_t* neg_heavy_rows, const int32_t* neg_heavy_first,
+                               const int32_t* d_neg_counts2, int64_t neg_max_heavy,
+                               float* neg_slab, float* out, hgnn_stream_t stream);
+
 /* ---- n_neg negatives per positive edge in the scoring pass (opt-in: neg_p of shape [E, k]) -----
  *   loss = <positive term> + 1/(E n_neg) sum_e sum_j softplus(<U[u_e],P[n_e,j]>)
  * The negatives are row-major [E, n_neg] in the user-grouped order: negative j of position p of

@@ -181,6 +181,16 @@ _SIGS = {
                                            _p, ctypes.c_float, _p, _p, _c_i64, _c_i64, _c_i32, _p,
                                            _p, _p]),
     "hgnn_uniform_i32": (_c_i32, [_p, _c_i64, _c_i32, _p, _p]),
+    "hgnn_weighted_cdf_ws_bytes": (_c_sz, [_c_i64]),
+    "hgnn_weighted_cdf_build": (_c_i32, [_p, _c_i64, _p, _p, _c_sz, _p]),
+    "hgnn_weighted_guide_build": (_c_i32, [_p, _c_i64, _c_i64, _c_i32, _c_i32, _p, _p]),
+    "hgnn_weighted_i32": (_c_i32, [_p, _c_i64, _p, _c_i64, _c_i64, _p, _c_i32, _c_i32, _p, _p]),
+    "hgnn_weighted_avoid_i32": (_c_i32, [_p, _c_i64, _c_i32, _p, _c_i64, _c_i64, _p, _c_i32,
+                                         _c_i32, _p, _c_i64, _p, _p, _c_i32, _p, _p, _p]),
+    "hgnn_plan_device": (_c_i32, [_p, _c_i64, _c_i32, _c_i64, _p, _p, _p, _p, _c_sz, _p]),
+    "hgnn_score_gather2_planned": (_c_i32, [_c_i32, _p, _c_i64, _p, _c_i32, _p, _p, _p, _p, _p,
+                                            _c_i64, _p, ctypes.c_float, _p, _p, _c_i64, _c_i64,
+                                            _c_i32, _p, _p, _p, _p, _c_i64, _p, _p, _p]),
     "hgnn_scale_unless_one": (_c_i32, [_p, _c_i64, _p, _p]),
     "hgnn_linear_fwd_f32": (_c_i32, [_p, _c_i64, _c_i32, _p, _c_i32, _p, _p, _p]),
     "hgnn_linear_dgrad_f32": (_c_i32, [_p, _c_i64, _c_i32, _p, _c_i32, _p, _p]),

@@ -972,6 +972,25 @@ __global__ void k_plan_scatter(const int32_t* heavy, const int32_t* hscan, const
   if (i == n) heavy_first[hscan[n]] = cscan[n];
 }
 
+// k_plan_scatter into arrays sized by a bound instead of by a count read back: at most
+// max_heavy rows are recorded, and the two counts stay on the device (hgnn_plan_device)
+__global__ void k_plan_scatter_bounded(const int32_t* heavy, const int32_t* hscan,
+                                       const int32_t* cscan, int64_t n, int64_t max_heavy,
+                                       int32_t* heavy_rows, int32_t* heavy_first,
+                                       int32_t* counts2) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n && heavy[i] && hscan[i] < max_heavy) {
+    heavy_rows[hscan[i]] = (int32_t)i;
+    heavy_first[hscan[i]] = cscan[i];
+  }
+  if (i == n) {
+    const int32_t nh = (int32_t)min<int64_t>(hscan[n], max_heavy);
+    heavy_first[nh] = cscan[n];
+    counts2[0] = nh;
+    counts2[1] = cscan[n];
+  }
+}
+
 __global__ void k_inv_degree(const int32_t* rowptr, int64_t n, float* inv) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -1029,6 +1048,20 @@ int hgnn_plan_fill(const int32_t* rowptr, int64_t n_rows, int32_t chunk, int32_t
   hipLaunchKernelGGL(k_plan_scatter, dim3(cdiv(n_rows + 1, 256)), dim3(256), 0, stream, heavy,
                      hscan, cscan, n_rows, heavy_rows, heavy_first);
   return check_launch("k_plan_scatter");
+}
+
+int hgnn_plan_device(const int32_t* rowptr, int64_t n_rows, int32_t chunk, int64_t max_heavy,
+                     int32_t* heavy_rows, int32_t* heavy_first, int32_t* d_counts2, void* ws,
+                     size_t ws_bytes, hgnn_stream_t stream_) {
+  hipStream_t stream = as_stream(stream_);
+  if (max_heavy < 0 || !heavy_rows || !heavy_first || !d_counts2)
+    return fail(HGNN_E_ARG, "plan_device: null pointer or max_heavy=%lld", (long long)max_heavy);
+  int32_t *heavy, *hscan, *cscan;
+  if (int rc = plan_common(rowptr, n_rows, chunk, ws, ws_bytes, stream, &heavy, &hscan, &cscan))
+    return rc;
+  hipLaunchKernelGGL(k_plan_scatter_bounded, dim3(cdiv(n_rows + 1, 256)), dim3(256), 0, stream,
+                     heavy, hscan, cscan, n_rows, max_heavy, heavy_rows, heavy_first, d_counts2);
+  return check_launch("k_plan_scatter_bounded");
 }
 
 int hgnn_inv_degree(const int32_t* rowptr, int64_t n_rows, float* inv_deg,

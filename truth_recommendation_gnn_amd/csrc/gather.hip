@@ -474,6 +474,150 @@ __global__ void __launch_bounds__(256) k_fixup(const GatherArgs a) {
   }
 }
 
+// ---------------------------------------------------------------- planned negatives (skewed)
+// hgnn_score_gather2_planned: the two-list score gather whose second list (the negatives) has a
+// heavy-row plan of its own.  Negatives drawn in proportion to popularity put a post's share of
+// all E k draws into its list, which k_gather would sum whole in the row's one wave.  Here a list
+// longer than `chunk` is summed chunk by chunk into a second slab, one wave per chunk with the
+// same segment_sum in mode 2; the row's own wave skips it, and k_fixup_neg adds the partial sums
+// to the row in chunk order after k_fixup has added the positives'.  The negatives change every
+// step, so their plan is made on the device (hgnn_plan_device) and nothing about it is known to
+// the host: the arrays and the grid are sized by the bound that the pair count gives, the counts
+// are read from device memory, and the waves and blocks beyond them return at once.
+// The kernels above are not touched: these are instantiations of their own.
+struct NegPlan {
+  const int32_t* heavy_rows;    // [max_heavy]
+  const int32_t* heavy_first;   // [max_heavy + 1]
+  const int32_t* counts;        // device {n_heavy, n_chunks}
+  float* slab;                  // [max_chunks * d]
+  int64_t max_heavy;
+  int64_t max_chunks;
+};
+
+// item: a row, a chunk of a row heavy in its positives (slab), or a chunk of a row heavy in its
+// negatives (NegPlan::slab), in that order
+template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, typename XT, int ZP>
+__device__ __forceinline__ void gather_item_pn(const GatherArgs& a, const NegPlan& p,
+                                               const int64_t item) {
+  using V = Vec<W>;
+  using S = RowSrc<XT, W>;
+  const int lane = threadIdx.x & 63;
+  const int sl = lane % LPR;
+  const bool writer = lane < LPR;
+  int64_t row, beg = 0, end = 0, beg2 = 0, end2 = 0;
+  float* dst;
+  if (item < a.n_rows) {                        // a row: the lists that are not heavy
+    row = item;
+    beg = a.rowptr[row];
+    end = a.rowptr[row + 1];
+    if (end - beg > a.chunk) end = beg;
+    beg2 = a.rowptr2[row];
+    end2 = a.rowptr2[row + 1];
+    if (end2 - beg2 > a.chunk) end2 = beg2;
+    dst = a.out + row * a.d;
+  } else if (item < a.n_items) {                // chunk of a row heavy in its positives
+    const int64_t slot = item - a.n_rows;
+    int64_t lo = 0, hi = a.n_heavy;
+    while (hi - lo > 1) {
+      int64_t mid = (lo + hi) >> 1;
+      if (a.heavy_first[mid] <= slot) lo = mid; else hi = mid;
+    }
+    row = a.heavy_rows[lo];
+    beg = a.rowptr[row] + (slot - a.heavy_first[lo]) * a.chunk;
+    end = min<int64_t>(beg + a.chunk, a.rowptr[row + 1]);
+    dst = a.slab + slot * a.d;
+  } else {                                      // chunk of a row heavy in its negatives
+    const int64_t slot = item - a.n_items;
+    const int64_t n_heavy = min<int64_t>(p.counts[0], p.max_heavy);
+    if (slot >= min<int64_t>(p.counts[1], p.max_chunks) || n_heavy < 1) return;
+    int64_t lo = 0, hi = n_heavy;
+    while (hi - lo > 1) {
+      int64_t mid = (lo + hi) >> 1;
+      if (p.heavy_first[mid] <= slot) lo = mid; else hi = mid;
+    }
+    row = p.heavy_rows[lo];
+    beg2 = a.rowptr2[row] + (slot - p.heavy_first[lo]) * a.chunk;
+    end2 = min<int64_t>(beg2 + a.chunk, a.rowptr2[row + 1]);
+    dst = p.slab + slot * a.d;
+  }
+  typename V::T acc[VPL], rv[VPL];
+#pragma unroll
+  for (int q = 0; q < VPL; ++q) {
+    acc[q] = V::zero();
+    const int c = (q * LPR + sl) * W;
+    rv[q] = c < a.d ? S::widen(S::load(static_cast<const XT*>(a.rowvec) + row * a.d + c))
+                    : V::zero();
+  }
+  segment_sum<LPR, VPL, W, UNROLL, HAS_W, true, false, XT, ZP>(a, a.col, 1, beg, end, rv, acc);
+  segment_sum<LPR, VPL, W, UNROLL, false, true, false, XT, ZP>(a, a.col2, 2, beg2, end2, rv, acc);
+  slot_combine<LPR, VPL, W>(acc);
+  if (!writer) return;
+#pragma unroll
+  for (int q = 0; q < VPL; ++q) {
+    const int c = (q * LPR + sl) * W;
+    if (c < a.d) {
+      if (a.nt_store) V::store_nt(dst + c, acc[q]);
+      else V::store(dst + c, acc[q]);
+    }
+  }
+}
+
+template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, typename XT>
+__global__ void __launch_bounds__(256) k_gather_pn(const GatherArgs a, const NegPlan p) {
+  const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (item >= a.n_items + p.max_chunks) return;
+  gather_item_pn<LPR, VPL, W, UNROLL, HAS_W, XT, 0>(a, p, item);
+}
+
+template <int LPR, int UNROLL, int ZP, bool EW>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
+k_gather_pn_zp(const GatherArgs a, const NegPlan p) {
+  const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (item >= a.n_items + p.max_chunks) return;
+  gather_item_pn<LPR, 1, 4, UNROLL, EW, float, ZP>(a, p, item);
+}
+
+// out[row] += sum_k slab[first + k] for the rows heavy in their negatives: k_fixup's slices and
+// fixed-order LDS tree, one block per possible heavy row (those beyond the device count return)
+template <int W>
+__global__ void __launch_bounds__(256) k_fixup_neg(const GatherArgs a, const NegPlan p) {
+  using V = Vec<W>;
+  __shared__ typename V::T buf[256];
+  const int64_t h = blockIdx.x;
+  if (h >= min<int64_t>(p.counts[0], p.max_heavy)) return;   // (uniform over the block)
+  const int64_t row = p.heavy_rows[h];
+  const int64_t f0 = p.heavy_first[h];
+  const int64_t f1 = min<int64_t>(p.heavy_first[h + 1], p.max_chunks);
+  const int nvec = (a.d + W - 1) / W;
+  int cpb = 1;
+  while (cpb < nvec && cpb < 256) cpb <<= 1;
+  const int S = 256 / cpb;
+  const int slice = threadIdx.x / cpb, cv = threadIdx.x % cpb;
+  for (int c0 = 0; c0 < nvec; c0 += cpb) {
+    const int c = (c0 + cv) * W;
+    typename V::T r = V::zero();
+    if (c < a.d)
+      for (int64_t k = f0 + slice; k < f1; k += S) V::add(r, V::load(p.slab + k * a.d + c));
+    buf[threadIdx.x] = r;
+    __syncthreads();
+    for (int st = S / 2; st >= 1; st >>= 1) {
+      if (slice < st) {
+        typename V::T t = buf[threadIdx.x];
+        V::add(t, buf[threadIdx.x + st * cpb]);
+        buf[threadIdx.x] = t;
+      }
+      __syncthreads();
+    }
+    if (slice == 0 && c < a.d) {
+      typename V::T t = buf[threadIdx.x];
+      float* o = a.out + row * a.d + c;
+      V::add(t, V::load(o));
+      V::store(o, t);
+    }
+    __syncthreads();
+  }
+}
+
 // ---------------------------------------------------------------------------------- host half
 // Every entry point is its own argument rules, gather_args (+ score_args / hot_args), run_gather;
 // run_gather validates, derives the Variant once and launches from the element type's width table.
@@ -722,6 +866,94 @@ static int run_score2(const char* who, Rows rows, const void* x, int64_t n_x, co
   return run_gather(a, n_x, as_stream(stream));
 }
 
+// The planned form's launches: the score gather of the element type's width table (per-edge
+// weights or not), then the two fix-ups in a fixed order.
+template <typename XT, int LPR, int VPL, int W, int UM, int UW, int US>
+static int launch_gather_pn(Shape<LPR, VPL, W, UM, UW, US>, const GatherArgs& a, const NegPlan& p,
+                            bool weighted, dim3 grid, hipStream_t stream) {
+  if (weighted)
+    hipLaunchKernelGGL((k_gather_pn<LPR, VPL, W, US, true, XT>), grid, dim3(256), 0, stream, a, p);
+  else
+    hipLaunchKernelGGL((k_gather_pn<LPR, VPL, W, US, false, XT>), grid, dim3(256), 0, stream, a, p);
+  return check_launch(sizeof(XT) == 2 ? "k_gather_pn(bf16)" : "k_gather_pn");
+}
+
+static int launch_gather_pn_zp(const GatherArgs& a, const NegPlan& p, bool weighted, dim3 grid,
+                               hipStream_t stream) {
+#define HGNN_GPZ(LPR, ZP)                                                                       \
+  do {                                                                                          \
+    if (weighted)                                                                               \
+      hipLaunchKernelGGL((k_gather_pn_zp<LPR, 4, ZP, true>), grid, dim3(256), 0, stream, a, p); \
+    else                                                                                        \
+      hipLaunchKernelGGL((k_gather_pn_zp<LPR, 4, ZP, false>), grid, dim3(256), 0, stream, a, p);\
+  } while (0)
+  if (a.d == 64) {
+    if (a.nt_load) HGNN_GPZ(16, 2); else HGNN_GPZ(16, 1);
+  } else {
+    if (a.nt_load) HGNN_GPZ(32, 2); else HGNN_GPZ(32, 1);
+  }
+#undef HGNN_GPZ
+  return check_launch("k_gather_pn(zp)");
+}
+
+static int run_score2_planned(Rows rows, const void* x, int64_t n_x, const void* rowvec, int32_t d,
+                              const int32_t* rowptr, const int32_t* col, const float* edge_w,
+                              const int32_t* rowptr_n, const int32_t* col_n, int64_t n_rows,
+                              const float* cscale, float inv_e, const int32_t* heavy_rows,
+                              const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
+                              int32_t chunk, float* slab, NegPlan p, float* out,
+                              hipStream_t stream) {
+  const char* who = "score_gather2_planned";
+  if (d <= 0 || n_rows < 0 || n_heavy < 0 || chunk <= 0 || p.max_heavy < 0)
+    return fail(HGNN_E_ARG, "%s: bad sizes d=%d n_rows=%lld chunk=%d", who, d, (long long)n_rows,
+                chunk);
+  if (rows == Rows::kBf16)
+    if (int rc = bf16_width_rule(d, who)) return rc;
+  if (rows == Rows::kZp && !zpack::width_ok(d))
+    return fail(HGNN_E_UNSUPPORTED, "%s: d=%d (zero-packed rows: 64 or 128)", who, d);
+  if (n_rows == 0) return HGNN_OK;
+  if (!rowptr || !rowptr_n || !rowvec || !cscale || !out)
+    return fail(HGNN_E_ARG, "%s: null rowptr / rowptr_n / rowvec / cscale / out", who);
+  if (n_heavy > 0 && (!heavy_rows || !heavy_first || !slab))
+    return fail(HGNN_E_ARG, "%s: heavy rows without plan/slab", who);
+  if (p.max_heavy > 0 && (!p.heavy_rows || !p.heavy_first || !p.counts || !p.slab))
+    return fail(HGNN_E_ARG, "%s: the negatives' plan has null arrays", who);
+  GatherArgs a = gather_args(x, d, rowptr, col, n_rows, edge_w, nullptr, nullptr, 0, 0,
+                             heavy_rows, heavy_first, n_heavy, n_chunks, chunk, slab, out);
+  score_args(a, rowvec, cscale, inv_e, 1, rowptr_n, col_n);
+  a.bf16 = rows == Rows::kBf16;
+  a.zp = rows == Rows::kZp;
+  nt_policy(a, n_x, elem_bytes(a));
+  const bool weighted = edge_w != nullptr;
+  const dim3 grid((unsigned)cdiv(a.n_items + p.max_chunks, 4));
+  int rc;
+  if (a.zp)
+    rc = launch_gather_pn_zp(a, p, weighted, grid, stream);
+  else if (a.bf16)
+    rc = with_shape_bf16(d, [&](auto s) {
+      return launch_gather_pn<uint16_t>(s, a, p, weighted, grid, stream);
+    });
+  else
+    rc = with_shape_f32(d, [&](auto s) {
+      return launch_gather_pn<float>(s, a, p, weighted, grid, stream);
+    });
+  if (rc) return rc;
+  // the fix-ups in a fixed order: the positives' partial sums, then the negatives'
+  if (a.n_heavy > 0) {
+    const dim3 fgrid((unsigned)a.n_heavy);
+    if (d % 4 == 0) hipLaunchKernelGGL(k_fixup<4>, fgrid, dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(k_fixup<1>, fgrid, dim3(256), 0, stream, a);
+    if (int rc2 = check_launch("k_fixup")) return rc2;
+  }
+  if (p.max_heavy > 0) {
+    const dim3 fgrid((unsigned)p.max_heavy);
+    if (d % 4 == 0) hipLaunchKernelGGL(k_fixup_neg<4>, fgrid, dim3(256), 0, stream, a, p);
+    else hipLaunchKernelGGL(k_fixup_neg<1>, fgrid, dim3(256), 0, stream, a, p);
+    return check_launch("k_fixup_neg");
+  }
+  return HGNN_OK;
+}
+
 }  // namespace hgnn
 
 using namespace hgnn;
@@ -942,6 +1174,28 @@ int hgnn_score_gather2_w_bf16(const uint16_t* x, int64_t n_x, const uint16_t* ro
   return run_score2("score_gather2_w_bf16", Rows::kBf16, x, n_x, rowvec, d, rowptr, col, rowptr_n,
                     col_n, n_rows, cscale, inv_e, heavy_rows, heavy_first, n_heavy, n_chunks, chunk,
                     slab, out, stream, true, edge_w);
+}
+
+int hgnn_score_gather2_planned(int32_t rows, const void* x, int64_t n_x, const void* rowvec,
+                               int32_t d, const int32_t* rowptr, const int32_t* col,
+                               const float* edge_w, const int32_t* rowptr_n, const int32_t* col_n,
+                               int64_t n_rows, const float* cscale, float inv_e,
+                               const int32_t* heavy_rows, const int32_t* heavy_first,
+                               int64_t n_heavy, int64_t n_chunks, int32_t chunk, float* slab,
+                               const int32_t* neg_heavy_rows, const int32_t* neg_heavy_first,
+                               const int32_t* d_neg_counts2, int64_t neg_max_heavy,
+                               float* neg_slab, float* out, hgnn_stream_t stream) {
+  if (rows < HGNN_ROWS_F32 || rows > HGNN_ROWS_ZP)
+    return fail(HGNN_E_ARG, "score_gather2_planned: rows=%d", rows);
+  NegPlan p{};
+  p.heavy_rows = neg_heavy_rows; p.heavy_first = neg_heavy_first; p.counts = d_neg_counts2;
+  p.slab = neg_slab;
+  p.max_heavy = neg_max_heavy;
+  p.max_chunks = 2 * neg_max_heavy;
+  const Rows r = rows == HGNN_ROWS_BF16 ? Rows::kBf16 : rows == HGNN_ROWS_ZP ? Rows::kZp : Rows::kF32;
+  return run_score2_planned(r, x, n_x, rowvec, d, rowptr, col, edge_w, rowptr_n, col_n, n_rows,
+                            cscale, inv_e, heavy_rows, heavy_first, n_heavy, n_chunks, chunk, slab,
+                            p, out, as_stream(stream));
 }
 
 }  // extern "C"

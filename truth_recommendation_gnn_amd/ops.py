@@ -588,13 +588,63 @@ def _score_gather(U, P, grouped, mode, cscale, inv_e, out, accumulate, tag):
             1 if accumulate else 0, N.stream_ptr(dev)), "hgnn_score_gather")
 
 
-def _score_gather2(U, P, pos, negs, cscale, inv_e, out, Uz=None, edge_w=None):
+class _NegPlan(NamedTuple):
+    """The heavy-row plan of one step's negatives' lists, on the device (``hgnn_plan_device``):
+    arrays sized by the bound ``max_heavy = pairs // chunk``, the counts never read back."""
+    heavy_rows: torch.Tensor      # int32 [max(max_heavy, 1)]
+    heavy_first: torch.Tensor     # int32 [max_heavy + 1]
+    counts: torch.Tensor          # int32 [2]: n_heavy, n_chunks
+    max_heavy: int
+    chunk: int
+
+
+def _plan_negatives(rowptr_n: torch.Tensor, n_posts: int, n_pairs: int, chunk: int) -> _NegPlan:
+    """The plan of the negatives' lists ``rowptr_n`` (``n_pairs`` entries over ``n_posts`` rows)
+    for the chunk of the positives' plan.  A list is heavy above ``chunk`` entries, so at most
+    ``n_pairs // chunk`` lists are, and they have at most twice that many chunks."""
+    dev = rowptr_n.device
+    lib = N.lib()
+    max_heavy = n_pairs // chunk
+    heavy_rows = torch.empty(max(max_heavy, 1), dtype=torch.int32, device=dev)
+    heavy_first = torch.empty(max_heavy + 1, dtype=torch.int32, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    ws = N.workspace(lib.hgnn_plan_ws_bytes(n_posts), dev)
+    with _timed("plan_negatives", 4 * n_posts * 10):
+        N.check(lib.hgnn_plan_device(N.ptr(rowptr_n), n_posts, chunk, max_heavy,
+                                     N.ptr(heavy_rows), N.ptr(heavy_first), N.ptr(counts),
+                                     N.ptr(ws), ws.numel(), N.stream_ptr(dev)),
+                "hgnn_plan_device")
+    return _NegPlan(heavy_rows, heavy_first, counts, max_heavy, chunk)
+
+
+def _score_gather2_planned(U, P, pos, negs, cscale, inv_e, out, Uz, edge_w, plan: _NegPlan,
+                           pplan: _PlanArgs, nb, cb):
+    """``_score_gather2`` through ``hgnn_score_gather2_planned``: the negatives' heavy lists go
+    chunk by chunk into a slab of their own, ``2 * max_heavy`` rows of d floats (the bound on the
+    chunks; at 200M pairs, chunk 1024 and d = 128 that is 200 MB), allocated per call."""
+    dev = out.device
+    d = int(out.shape[1])
+    n = pos.n_rows
+    if plan.chunk != pos.plan.chunk:
+        raise ValueError("edge_bce_loss: the negatives' plan was made for another chunk")
+    rows, table = ((1, U) if U.dtype == torch.bfloat16 else (2, Uz) if Uz is not None else (0, U))
+    neg_slab = torch.empty(max(2 * plan.max_heavy, 1) * d, dtype=torch.float32, device=dev)
+    with _timed(f"score_gather_planned[{n}<-{U.shape[0]}]x{d}", nb, cb):
+        N.check(N.lib().hgnn_score_gather2_planned(
+            rows, N.ptr(table), U.shape[0], N.ptr(P), d, N.ptr(pos.rowptr), N.ptr(pos.col),
+            N.ptr(edge_w), N.ptr(negs.rowptr), N.ptr(negs.col), n, N.ptr(cscale), inv_e, *pplan,
+            N.ptr(plan.heavy_rows), N.ptr(plan.heavy_first), N.ptr(plan.counts), plan.max_heavy,
+            N.ptr(neg_slab), N.ptr(out), N.stream_ptr(dev)), "hgnn_score_gather2_planned")
+
+
+def _score_gather2(U, P, pos, negs, cscale, inv_e, out, Uz=None, edge_w=None, neg_plan=None):
     """Both dP gathers in one pass (hgnn_score_gather2): row r sums its positive edges (mode 1,
     heavy-row plan) and its negatives (mode 2) into one accumulator and writes dP[r] once.
     ``Uz``: ``zpack_rows(U)``; the gather then reads the packed rows (same sums, bit for bit;
     the timer entry keeps its name and the unpacked table's algorithmic bytes).  ``edge_w``: the
     positives' per-edge weights by position of ``pos`` (the ``_w`` entries; 4 B more per
-    positive edge)."""
+    positive edge).  ``neg_plan``: the ``_NegPlan`` of ``SkewedNegatives``; the gather is then
+    ``hgnn_score_gather2_planned``."""
     dev = out.device
     d = int(out.shape[1])
     n = pos.n_rows
@@ -604,6 +654,10 @@ def _score_gather2(U, P, pos, negs, cscale, inv_e, out, Uz=None, edge_w=None):
     wb = 4 * int(pos.col.numel()) if edge_w is not None else 0
     nb = gather_bytes(E, n, d, False, rb) + 4 * (n + 1) + n * rb + wb
     cb = gather_compulsory_bytes(E, n, int(U.shape[0]), d, False, rb) + 4 * (n + 1) + n * rb + wb
+    if neg_plan is not None:
+        _score_gather2_planned(U, P, pos, negs, cscale, inv_e, out, Uz, edge_w, neg_plan, plan,
+                               nb, cb)
+        return
     # the entry point by the rows it reads: bf16, zero-packed fp32, fp32
     rows, table = (("_bf16", U) if U.dtype == torch.bfloat16 else
                    ("_zp", Uz) if Uz is not None else ("", U))
@@ -1584,8 +1638,14 @@ def link_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: torch.T
     ``mean_e(w_e * softplus(-s_e)) + mean_e softplus(s_neg_e)``.
 
     ``neg_p`` of shape ``[E, k]``: k negatives per positive edge, the same lines with a 2-D draw;
-    the negatives' term is then the mean over all E·k scores (``[E, 1]`` is ``[E]``)."""
+    the negatives' term is then the mean over all E·k scores (``[E, 1]`` is ``[E]``).
+
+    ``SkewedNegatives`` carry no order of their own here: pass their ``.values``, row e being the
+    negatives of ``pos_edges[:, e]`` (for :func:`sample_negatives`' user-grouped draws, with the
+    edges in that order)."""
     _weighting_value(weighting, "link_loss")
+    if isinstance(neg_p, SkewedNegatives):
+        raise TypeError("link_loss: pass SkewedNegatives.values, in the order of pos_edges")
     pos_u, pos_p = pos_edges[0], pos_edges[1]
     u = user_emb[pos_u]
     pos_scores = (u * post_emb[pos_p]).sum(dim=1)
@@ -1693,11 +1753,14 @@ class _Negatives(NamedTuple):
     i32: Optional[torch.Tensor]
     draw: Optional["NegativeDraw"]
     k: int = 1      # negatives per positive edge: the tensors are row-major [E, k]
+    planned: bool = False   # ``SkewedNegatives``: the dP gather plans their lists per step
 
     @classmethod
     def of(cls, neg_u_order, E: int, n_posts: int) -> "_Negatives":
         """``neg_u_order`` checked against the ``E`` positive edges and ``n_posts``."""
         k = _neg_count(neg_u_order, E, "edge_bce_loss")
+        if isinstance(neg_u_order, SkewedNegatives):
+            return cls(None, neg_u_order.values.contiguous(), None, k, True)
         if isinstance(neg_u_order, NegativeDraw):
             if neg_u_order.num_posts != n_posts:
                 raise ValueError("edge_bce_loss: the NegativeDraw does not match the positive "
@@ -1785,15 +1848,27 @@ class PresortedNegatives:
     sorts them under a collective, ahead of the loss that consumes them.  It holds the grouping
     and the draws it was made from (the objects themselves, compared with ``is``: an id could be
     reused by a new object once the old one is freed), so a loss over other edges or other
-    draws is refused."""
+    draws is refused.  ``plan``: the ``_NegPlan`` of ``SkewedNegatives`` (made with the grouping,
+    on the device), None for plain negatives; a loss over the other kind is refused."""
 
-    def __init__(self, csr, neg_p, neg_order: str, n_posts: int, rowptr, users, k: int = 1):
+    def __init__(self, csr, neg_p, neg_order: str, n_posts: int, rowptr, users, k: int = 1,
+                 plan=None):
         self.csr, self.neg_p, self.neg_order = csr, neg_p, neg_order
         self.n_posts = int(n_posts)
         self.rowptr, self.users = rowptr, users
         self.k = int(k)            # negatives per positive edge the grouping holds
+        self.plan = plan
+
+    @property
+    def planned(self) -> bool:
+        return self.plan is not None
 
     def check_draws(self, neg_p, neg_order: str, where: str) -> None:
+        if isinstance(neg_p, SkewedNegatives) != self.planned:
+            raise ValueError(f"{where}: the presorted negatives were grouped "
+                             f"{'with' if self.planned else 'without'} a plan of their lists "
+                             f"({'SkewedNegatives' if self.planned else 'plain negatives'}), the "
+                             "loss got the other kind")
         if neg_order != self.neg_order:
             raise ValueError(f"{where}: presorted negatives were grouped with neg_order="
                              f"{self.neg_order!r}, the loss got neg_order={neg_order!r}")
@@ -1819,7 +1894,9 @@ def presort_negatives(n_users: int, n_posts: int, pos_edges: torch.Tensor, neg_p
     only the edges and the draws, not the embeddings); pass it back as ``presorted=`` with the
     same ``neg_p`` and ``neg_order`` (required here: the two loss entry points default to
     different orders).  ``neg_p`` of shape ``[E, k]`` (or a ``NegativeDraw`` made for k): the
-    grouping of all E·k negatives, for a loss over the same k."""
+    grouping of all E·k negatives, for a loss over the same k.  ``SkewedNegatives``
+    (``neg_order="user"``): the plan of their lists is made here too, on the device, and the
+    loss must get the same ``SkewedNegatives``."""
     k = _neg_count(neg_p, int(pos_edges.shape[1]), "presort_negatives")
     csr = relation_csr_for_loss(pos_edges, n_users, n_posts)
     E = csr.num_edges
@@ -1827,7 +1904,8 @@ def presort_negatives(n_users: int, n_posts: int, pos_edges: torch.Tensor, neg_p
     dev = csr.fwd.rowptr.device
     err = torch.zeros(2, dtype=torch.int32, device=dev)
     rp, us = _sort_negatives(negs, _user_of_draw(csr, k), E * k, n_posts, err, dev)
-    return PresortedNegatives(csr, neg_p, neg_order, n_posts, rp, us, k)
+    plan = _plan_negatives(rp, n_posts, E * k, csr.fwd.plan.chunk) if negs.planned else None
+    return PresortedNegatives(csr, neg_p, neg_order, n_posts, rp, us, k, plan)
 
 
 def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total: int,
@@ -1869,6 +1947,9 @@ def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total:
                 torch.zeros(U.shape, dtype=torch.float32, device=dev),
                 torch.zeros(P.shape, dtype=torch.float32, device=dev))
     negs = _Negatives.of(neg_u_order, E, np_)
+    if negs.planned and sharded:
+        raise ValueError("edge_bce_loss: SkewedNegatives do not combine with ready / on_dP / "
+                         "p_chunks (the sharded step gathers dP by row blocks, without a plan)")
     if negs.k >= 2 and sharded:
         raise ValueError(f"edge_bce_loss: {negs.k} negatives per positive edge do not combine "
                          "with ready / on_dP / p_chunks (the sharded step draws one per edge)")
@@ -1922,12 +2003,18 @@ def _loss_dP(U, P, csr: RelationCSR, negs: _Negatives, c, inv_e, err, relu_out: 
     dev = U.device
     np_, E, pf = P.shape[0], csr.num_edges, csr.fwd
     dP = torch.empty(P.shape, dtype=torch.float32, device=dev)
+    neg_plan = None
     if presorted is not None:
         presorted.check_edges(csr, np_, negs.k)
-        rowptr_n, nu_s = presorted.rowptr, presorted.users
+        if presorted.planned != negs.planned:
+            raise ValueError("edge_bce_loss: the presorted negatives are of the other kind "
+                             "(planned: SkewedNegatives; unplanned: plain negatives)")
+        rowptr_n, nu_s, neg_plan = presorted.rowptr, presorted.users, presorted.plan
     else:
         rowptr_n, nu_s = _sort_negatives(negs, _user_of_draw(csr, negs.k), E * negs.k, np_, err,
                                          dev)
+        if negs.planned:
+            neg_plan = _plan_negatives(rowptr_n, np_, E * negs.k, pf.plan.chunk)
     if ready is not None and p_chunks is None:
         # P is still arriving (parallel.py's all-gather of the post table): the sort above
         # needs only the edges, so it ran ahead; every kernel below reads P
@@ -1949,7 +2036,7 @@ def _loss_dP(U, P, csr: RelationCSR, negs: _Negatives, c, inv_e, err, relu_out: 
     if U.dtype != torch.bfloat16 and ready is None and zpack_on(U, relu_out):
         Uz = zpack_rows(U)
     _score_gather2(U, P, pf, GroupedEdges(rowptr_n, nu_s, nu_s, no_plan, np_), c, inv_e, dP, Uz,
-                   edge_w)
+                   edge_w, neg_plan)
     return dP
 
 
@@ -2094,6 +2181,14 @@ def edge_bce_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: tor
     ``HGNN_ZPACK``, ``presorted``, ``check`` and ``n_edges_total`` / ``cscale``; with ``ready`` it
     is an error (the sharded step draws one negative per edge).
 
+    ``neg_p`` a :class:`SkewedNegatives` (``neg_order="user"``; :func:`sample_negatives` with
+    ``distribution`` / ``avoid``, or a caller's own int32 tensor marked that way): the same loss,
+    the dP gather through ``hgnn_score_gather2_planned`` — the negatives' lists get a heavy-row
+    plan on the device every step (no host sync), so draws piled on popular posts are summed by
+    many waves.  It combines with both weightings, k >= 1, ``row_dtype="bf16"``, ``HGNN_ZPACK``
+    and a ``presorted`` made from the same ``SkewedNegatives``; with ``ready`` it is an error.
+    Plain tensors and ``NegativeDraw`` keep the unplanned gather.
+
     ``neg_order='edge'``: ``neg_p[e]`` is the negative of COO edge e (the reference's layout);
     ``'user'``: already in the user-grouped order (what :func:`sample_negatives` draws).
     ``check`` costs one host sync (the reference syncs every step with ``loss.item()``).
@@ -2112,6 +2207,7 @@ def edge_bce_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: tor
                                {"cscale": cscale, "n_edges_total": n_edges_total,
                                 "ready": ready})
     _neg_count(neg_p, int(pos_edges.shape[1]), "edge_bce_loss", {"ready": ready})
+    _skewed_rules(neg_p, neg_order, "edge_bce_loss", {"ready": ready})
     bf16 = resolve_row_dtype(row_dtype) == "bf16"
     if bf16 and ready is not None:
         if row_dtype is not None:
@@ -2158,13 +2254,16 @@ def edge_bce_loss_raw(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges:
 
     ``neg_p`` of shape ``[E, k]``: :func:`edge_bce_loss`'s k negatives per positive edge
     (``n_edges_total`` stays the number of positive edges); with k >= 2, ``ready`` / ``on_dP`` /
-    ``p_chunks`` are errors."""
+    ``p_chunks`` are errors.  A :class:`SkewedNegatives` (``neg_order="user"``): the planned dP
+    gather, as in :func:`edge_bce_loss`; ``ready`` / ``on_dP`` / ``p_chunks`` are errors."""
     per_edge = _edge_weighting("edge_bce_loss_raw", weighting, pos_weights,
                                int(pos_edges.shape[1]),
                                {"cscale": cscale, "n_edges_total": n_edges_total, "ready": ready,
                                 "on_dP": on_dP, "p_chunks": p_chunks})
     _neg_count(neg_p, int(pos_edges.shape[1]), "edge_bce_loss_raw",
                {"ready": ready, "on_dP": on_dP, "p_chunks": p_chunks})
+    _skewed_rules(neg_p, neg_order, "edge_bce_loss_raw",
+                  {"ready": ready, "on_dP": on_dP, "p_chunks": p_chunks})
     if not per_edge and (cscale is None or n_edges_total is None):
         raise ValueError("edge_bce_loss_raw: weighting='mean' needs n_edges_total and cscale")
     if _row_dtype_value(row_dtype, "row_dtype") == "bf16":
@@ -2187,6 +2286,10 @@ def edge_bce_loss_raw(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges:
 
 
 def _negatives_user_order(csr, neg_p, neg_order):
+    if isinstance(neg_p, SkewedNegatives):
+        if neg_order != "user":
+            raise ValueError("SkewedNegatives are in the user-grouped order (neg_order='user')")
+        return neg_p
     if isinstance(neg_p, NegativeDraw):
         if neg_order != "user":
             raise ValueError("a NegativeDraw is drawn in the user-grouped order (neg_order='user')")
@@ -2224,6 +2327,126 @@ class NegativeDraw:
         return out
 
 
+class SkewedNegatives:
+    """Negatives whose lists per post may be far from even (drawn by popularity,
+    :func:`sample_negatives` with ``distribution`` / ``avoid``): a thin holder of the int32
+    ``[E]`` / ``[E, k]`` tensor in the user-grouped order (``.values``).  The loss entry points
+    take it with ``neg_order="user"`` and give the dP gather a per-step plan of the negatives'
+    lists, so a post drawn a million times is summed by many waves and not by one.
+    ``SkewedNegatives(tensor)`` marks negatives of the caller's own that way; the plain-torch
+    :func:`link_loss` takes ``.values`` in the order of its edges."""
+
+    def __init__(self, values: torch.Tensor):
+        if not isinstance(values, torch.Tensor) or values.dtype != torch.int32 or \
+                values.dim() not in (1, 2):
+            raise ValueError("SkewedNegatives: an int32 tensor of shape [E] or [E, k] in the "
+                             "user-grouped order is required")
+        self.values = values
+
+    @property
+    def shape(self):
+        return self.values.shape
+
+    @property
+    def dtype(self):
+        return self.values.dtype
+
+    @property
+    def device(self):
+        return self.values.device
+
+    def dim(self) -> int:
+        return self.values.dim()
+
+
+def _skewed_rules(neg_p, neg_order: str, who: str, sharded) -> None:
+    """``SkewedNegatives`` checked before anything touches the device: the user-grouped order
+    only, and never with the sharded step's arguments ({name: value}, None when not given)."""
+    if not isinstance(neg_p, SkewedNegatives):
+        return
+    if neg_order != "user":
+        raise ValueError(f"{who}: SkewedNegatives are in the user-grouped order "
+                         "(neg_order='user')")
+    given = [a for a, v in sharded.items() if v is not None]
+    if given:
+        raise ValueError(f"{who}: SkewedNegatives do not combine with {' / '.join(given)} (the "
+                         "sharded step gathers dP by row blocks, without a plan of the "
+                         "negatives' lists)")
+
+
+class PostDistribution:
+    """A distribution over the posts to draw negatives from (:func:`sample_negatives`), as the
+    device table the draw kernels read.
+
+    ``weights``: ``[num_posts]``.  A floating tensor must be finite, >= 0 and not all zero; it is
+    quantised elementwise to integers, ``q = floor(w.double() / w.double().max() * (2^32 - 1))``,
+    so a weight below ``max * 2^-32`` becomes 0 and that post is never drawn.  An integer tensor
+    is taken as ``q`` itself (each in [0, 2^32), not all zero).  Post j is drawn with probability
+    ``q[j] / T``, ``T = sum(q)``: draw c maps ``r = (splitmix64(seed + c * golden) * T) >> 64`` to
+    the post with ``cdf[j] <= r < cdf[j + 1]`` (``cdf``: the exclusive sums of ``q``, int64, exact).
+
+    It holds ``q``, ``cdf`` (``[num_posts + 1]``), ``T`` (read back once, here) and the guide table
+    of the search: ``n_guide`` buckets of ``2^shift`` values of ``r`` each, as many buckets as
+    posts (a power of two, at most 2^20: 4 MB beside 8 MB of cdf at 1M posts)."""
+
+    GUIDE_MAX = 1 << 20
+
+    def __init__(self, weights: torch.Tensor):
+        if not isinstance(weights, torch.Tensor) or weights.dim() != 1 or weights.numel() < 1 or \
+                weights.is_complex() or weights.dtype == torch.bool:
+            raise ValueError("PostDistribution: weights must be a real [num_posts] tensor")
+        if weights.numel() >= 2**31:
+            raise ValueError("PostDistribution: num_posts must be below 2^31")
+        if weights.is_floating_point():
+            w = weights.detach().double()
+            if not bool(torch.isfinite(w).all()):
+                raise ValueError("PostDistribution: weights must be finite")
+            if bool((w < 0).any()):
+                raise ValueError("PostDistribution: weights must be >= 0")
+            top = w.max()
+            if float(top) == 0.0:
+                raise ValueError("PostDistribution: weights are all zero")
+            q = torch.floor(w / top * float(2**32 - 1)).to(torch.int64)
+        else:
+            q = weights.detach().to(torch.int64)
+            if bool((q < 0).any()) or bool((q >= 2**32).any()):
+                raise ValueError("PostDistribution: integer weights must lie in [0, 2^32)")
+            if not bool((q > 0).any()):
+                raise ValueError("PostDistribution: weights are all zero")
+        dev = N.require_device(weights)
+        lib, s = N.lib(), N.stream_ptr(dev)
+        self.num_posts = int(q.numel())
+        self.q = q.contiguous()
+        self.cdf = torch.empty(self.num_posts + 1, dtype=torch.int64, device=dev)
+        ws = N.workspace(lib.hgnn_weighted_cdf_ws_bytes(self.num_posts), dev)
+        N.check(lib.hgnn_weighted_cdf_build(N.ptr(self.q), self.num_posts, N.ptr(self.cdf),
+                                            N.ptr(ws), ws.numel(), s), "hgnn_weighted_cdf_build")
+        self.T = int(self.cdf[-1])              # host sync: once per distribution
+        gbits = min(max(self.num_posts - 1, 1).bit_length(), self.GUIDE_MAX.bit_length() - 1)
+        self.n_guide = 1 << gbits
+        self.shift = max((self.T - 1).bit_length() - gbits, 0)
+        self.guide = torch.empty(self.n_guide + 1, dtype=torch.int32, device=dev)
+        N.check(lib.hgnn_weighted_guide_build(N.ptr(self.cdf), self.num_posts, self.T, self.shift,
+                                              self.n_guide, N.ptr(self.guide), s),
+                "hgnn_weighted_guide_build")
+
+    @classmethod
+    def from_degree(cls, pos_edges: torch.Tensor, num_posts: int,
+                    power: float = 0.75) -> "PostDistribution":
+        """Posts in proportion to ``in_degree ** power`` over ``pos_edges`` (``[2, E]``, row 1 the
+        posts): word2vec's unigram^0.75 negatives.  A post without a positive edge is never
+        drawn."""
+        deg = torch.bincount(pos_edges[1].to(torch.int64), minlength=int(num_posts))
+        if deg.numel() != int(num_posts):
+            raise ValueError(f"PostDistribution.from_degree: a post index of {num_posts} or more")
+        return cls(deg.double() ** float(power))
+
+    def _table_args(self):
+        """cdf, n_posts, T, guide, shift, n_guide in ABI order."""
+        return (N.ptr(self.cdf), self.num_posts, self.T, N.ptr(self.guide), self.shift,
+                self.n_guide)
+
+
 def _num_neg_value(num_neg: int) -> int:
     if int(num_neg) != num_neg or num_neg < 1:
         raise ValueError(f"num_neg={num_neg!r}; expected a whole number of at least 1 negative "
@@ -2240,10 +2463,18 @@ def _draw_count(E: int, num_neg: int) -> int:
 
 def draw_negatives(pos_edges: torch.Tensor, num_posts: int,
                    generator: Optional[torch.Generator] = None,
-                   num_neg: int = 1) -> NegativeDraw:
+                   num_neg: int = 1, *, distribution=None, avoid=None) -> NegativeDraw:
     """:func:`sample_negatives` without the materialised array: the seed only (one tiny device
     draw from ``generator``, no host sync).  ``edge_bce_loss(..., neg_order='user')`` takes it.
-    ``num_neg`` = k > 1: E·k draws, shape ``(E, k)``."""
+    ``num_neg`` = k > 1: E·k draws, shape ``(E, k)``.
+
+    Uniform draws only: ``distribution`` / ``avoid`` raise ``ValueError``.  A ``NegativeDraw`` is
+    drawn again in the two kernels that read it, and a table search plus a rejection loop would
+    be paid twice there; :func:`sample_negatives` materialises the weighted draws instead."""
+    if distribution is not None or avoid is not None:
+        raise ValueError("draw_negatives: distribution / avoid are not drawn lazily (the search "
+                         "and the rejection loop would run in both kernels that regenerate the "
+                         "draws); use sample_negatives, which materialises them")
     num_neg = _num_neg_value(num_neg)
     dev = N.require_device(pos_edges)
     if num_posts < 1 or num_posts >= 2**31:
@@ -2255,7 +2486,9 @@ def draw_negatives(pos_edges: torch.Tensor, num_posts: int,
 
 def sample_negatives(pos_edges: torch.Tensor, num_posts: int,
                      generator: Optional[torch.Generator] = None,
-                     num_neg: int = 1) -> torch.Tensor:
+                     num_neg: int = 1, *, distribution: Optional["PostDistribution"] = None,
+                     avoid=None, max_tries: int = 4,
+                     kept_seen: Optional[torch.Tensor] = None):
     """One uniform negative post per positive edge (train_gnn.py:272's ``torch.randint``), drawn
     directly in the user-grouped order: the draws are iid, so only their labels move.
     ``num_neg`` = k > 1: k per positive edge, ``[E, k]`` (row p the negatives of user-grouped
@@ -2263,8 +2496,21 @@ def sample_negatives(pos_edges: torch.Tensor, num_posts: int,
 
     int32 draws from ``hgnn_uniform_i32`` (a counter-based generator seeded from ``generator``
     on the device, no host sync): in range by construction, so the loss sorts them without the
-    int64 validation pass.  ``edge_bce_loss`` also takes int64 ``torch.randint`` negatives."""
+    int64 validation pass.  ``edge_bce_loss`` also takes int64 ``torch.randint`` negatives.
+
+    ``distribution`` (a :class:`PostDistribution`): the draws follow it instead
+    (``hgnn_weighted_i32``; draw p·k + j is negative j of position p).  ``avoid`` (a
+    ``metrics.SeenIndex``): a draw that the position's user has seen is drawn again, up to
+    ``max_tries`` attempts in all (``hgnn_weighted_avoid_i32``; attempt 0 is the draw without
+    ``avoid``); when every attempt is seen the last is kept and ``kept_seen``, an optional
+    one-element int64 device tensor, is incremented on the device.  ``avoid`` alone rejects
+    uniform draws.  With either argument the result is a :class:`SkewedNegatives` (``.values``:
+    the tensor), which the loss takes with ``neg_order="user"``; the positions are those of the
+    cached ``relation_csr`` the loss uses.  Without them this is the function it was."""
     num_neg = _num_neg_value(num_neg)
+    if distribution is not None or avoid is not None:
+        return _sample_skewed(pos_edges, num_posts, generator, num_neg, distribution, avoid,
+                              max_tries, kept_seen)
     dev = N.require_device(pos_edges)
     E = int(pos_edges.shape[1])
     out = torch.empty(E if num_neg == 1 else (E, num_neg), dtype=torch.int32, device=dev)
@@ -2278,6 +2524,50 @@ def sample_negatives(pos_edges: torch.Tensor, num_posts: int,
     N.check(N.lib().hgnn_uniform_i32(N.ptr(seed), n, int(num_posts), N.ptr(out),
                                      N.stream_ptr(dev)), "hgnn_uniform_i32")
     return out
+
+
+def _sample_skewed(pos_edges, num_posts: int, generator, num_neg: int, distribution, avoid,
+                   max_tries: int, kept_seen) -> SkewedNegatives:
+    """:func:`sample_negatives` with ``distribution`` and / or ``avoid``."""
+    if distribution is not None and not isinstance(distribution, PostDistribution):
+        raise ValueError("sample_negatives: distribution must be a PostDistribution")
+    if int(max_tries) != max_tries or max_tries < 1:
+        raise ValueError(f"sample_negatives: max_tries={max_tries!r}; at least 1 attempt")
+    if num_posts < 1 or num_posts >= 2**31:
+        raise ValueError(f"num_posts={num_posts} out of range")
+    if distribution is not None and distribution.num_posts != int(num_posts):
+        raise ValueError(f"sample_negatives: the distribution is over {distribution.num_posts} "
+                         f"posts, num_posts={num_posts}")
+    if avoid is not None and avoid.num_posts != int(num_posts):
+        raise ValueError(f"sample_negatives: avoid indexes {avoid.num_posts} posts, "
+                         f"num_posts={num_posts}")
+    if kept_seen is not None and (avoid is None or kept_seen.dtype != torch.int64
+                                  or kept_seen.numel() != 1):
+        raise ValueError("sample_negatives: kept_seen is a one-element int64 tensor, with avoid")
+    dev = N.require_device(pos_edges, kept_seen)
+    E = int(pos_edges.shape[1])
+    out = torch.empty(E if num_neg == 1 else (E, num_neg), dtype=torch.int32, device=dev)
+    if E == 0:
+        return SkewedNegatives(out)
+    n = _draw_count(E, num_neg)
+    lib, s = N.lib(), N.stream_ptr(dev)
+    seed = torch.randint(0, 2**62, (1,), device=dev, dtype=torch.int64, generator=generator)
+    table = (distribution._table_args() if distribution is not None
+             else (None, int(num_posts), 0, None, 0, 0))
+    if avoid is None:
+        # per draw a seed-free counter in, 4 B out, and a few 8-B cdf entries from the caches
+        with _timed("weighted_negatives", 4 * n):
+            N.check(lib.hgnn_weighted_i32(N.ptr(seed), n, *table, N.ptr(out), s),
+                    "hgnn_weighted_i32")
+        return SkewedNegatives(out)
+    csr = relation_csr_for_loss(pos_edges, avoid.num_users, num_posts)
+    uop = _user_of_pos(csr)
+    with _timed("weighted_negatives_avoid", (4 + 4) * n):
+        N.check(lib.hgnn_weighted_avoid_i32(
+            N.ptr(seed), n, num_neg, *table, N.ptr(uop), avoid.num_users, N.ptr(avoid.rowptr),
+            N.ptr(avoid._col), int(max_tries), N.ptr(out), N.ptr(kept_seen), s),
+            "hgnn_weighted_avoid_i32")
+    return SkewedNegatives(out)
 
 
 # ----------------------------------------------------------------------------- composable ops
