@@ -693,6 +693,70 @@ int hgnn_edge_score_fwd_k_bf16(const uint16_t* U, const uint16_t* P, int32_t d, 
                                int64_t n_edges, const float* cscale, float* dU, float* part,
                                float* loss, int32_t* err, hgnn_stream_t stream);
 
+/* ---- logQ correction of the link loss's scores (opt-in: logq= of the loss entry points) --------
+ * A per-post table b (fp32 [n_posts], a constant: no gradient into it) moves the logit of every
+ * scored pair, positive and negative alike:
+ *   z(u, p) = <U[u], P[p]> - b[p]
+ *   loss = <scales as below> sum softplus(-z_pos) + sum softplus(z_neg)
+ *   dU[u] = sum h P[.],  dP[p] = sum h U[.],  h = scale * (sigmoid(z_pos) - 1)  or  scale * sigmoid(z_neg)
+ * With b[p] = log(k Q(p)) for negatives drawn k per edge from Q this is the logQ correction of
+ * sampled softmax / NCE.  The dot products, the rows read, the sums and their order are those of
+ * the entries these stand beside; only the scalar fed to the sigmoid and the softplus moves, and
+ * the positives' coefficient sigmoid(z) - 1 is formed as -sigmoid(-z) from the same exponential
+ * (b = log(1/T) puts z near +22, where the difference is exactly 0 in fp32), so b = 0 gives their
+ * results to rounding, and two runs are bitwise equal.  With bf16 rows b stays fp32.
+ *
+ * hgnn_edge_score_fwd_k_lq: hgnn_edge_score_fwd_k (any n_neg >= 1, edge_w nullable) with
+ * post_bias = b.  Scaling convention: hgnn_edge_score_fwd_k's, n_edges = E * n_neg and
+ * *cscale = c * n_neg.  Written: dU, part, loss and err; the per-position outputs of
+ * hgnn_edge_score_fwd are not produced.  An out-of-range negative is counted into err, reads
+ * post_bias[0] as it reads post 0, and contributes nothing.  post_bias == NULL is HGNN_E_ARG, the
+ * rest as for hgnn_edge_score_fwd_k; all before any launch. */
+int hgnn_edge_score_fwd_k_lq(const float* U, const float* P, int32_t d, int64_t n_users,
+                             int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
+                             const float* edge_w, const int64_t* neg_i64, const int32_t* neg_i32,
+                             const uint64_t* d_seed, int32_t n_neg, int64_t n_edges,
+                             const float* cscale, const float* post_bias, float* dU, float* part,
+                             float* loss, int32_t* err, hgnn_stream_t stream);
+/* ... with bf16 U and P (d % 8 == 0 and d <= 512, else HGNN_E_UNSUPPORTED); post_bias fp32. */
+int hgnn_edge_score_fwd_k_lq_bf16(const uint16_t* U, const uint16_t* P, int32_t d,
+                                  int64_t n_users, int64_t n_posts, const int32_t* rowptr_u,
+                                  const int32_t* col_u, const float* edge_w,
+                                  const int64_t* neg_i64, const int32_t* neg_i32,
+                                  const uint64_t* d_seed, int32_t n_neg, int64_t n_edges,
+                                  const float* cscale, const float* post_bias, float* dU,
+                                  float* part, float* loss, int32_t* err, hgnn_stream_t stream);
+/* hgnn_score_gather2 / _w / _zp / _bf16 with the offset: the post is the output row, so the wave
+ * of an item (a row, or a chunk of a heavy row) reads row_bias[row] once, beside rowvec[row], and
+ * subtracts it from every score of both lists before the sigmoid.  rows: the format of x and
+ * rowvec (HGNN_ROWS_*, hgnn_score_gather2_planned's); edge_w: the positives' per-edge weights or
+ * NULL; cscale and inv_e as hgnn_score_gather2 takes them.  Written: out (every row once) and the
+ * slab; the slab and the fix-up hold sums and read no offset.  rows out of range and
+ * row_bias == NULL are HGNN_E_ARG, a width the format does not take HGNN_E_UNSUPPORTED, then
+ * hgnn_score_gather2's rules; all before any launch. */
+int hgnn_score_gather2_lq(int32_t rows, const void* x, int64_t n_x, const void* rowvec, int32_t d,
+                          const int32_t* rowptr, const int32_t* col, const float* edge_w,
+                          const int32_t* rowptr_n, const int32_t* col_n, int64_t n_rows,
+                          const float* cscale, float inv_e, const float* row_bias,
+                          const int32_t* heavy_rows, const int32_t* heavy_first, int64_t n_heavy,
+                          int64_t n_chunks, int32_t chunk, float* slab, float* out,
+                          hgnn_stream_t stream);
+/* hgnn_score_gather2_planned with the offset (its arguments, row_bias after inv_e): whole rows,
+ * chunks of a row heavy in its positives and chunks of a row heavy in its negatives all subtract
+ * row_bias[row]; the two slabs and the two fix-ups are unchanged.  rows out of range and
+ * row_bias == NULL are HGNN_E_ARG, then hgnn_score_gather2_planned's rules; all before any
+ * launch. */
+int hgnn_score_gather2_planned_lq(int32_t rows, const void* x, int64_t n_x, const void* rowvec,
+                                  int32_t d, const int32_t* rowptr, const int32_t* col,
+                                  const float* edge_w, const int32_t* rowptr_n,
+                                  const int32_t* col_n, int64_t n_rows, const float* cscale,
+                                  float inv_e, const float* row_bias, const int32_t* heavy_rows,
+                                  const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
+                                  int32_t chunk, float* slab, const int32_t* neg_heavy_rows,
+                                  const int32_t* neg_heavy_first, const int32_t* d_neg_counts2,
+                                  int64_t neg_max_heavy, float* neg_slab, float* out,
+                                  hgnn_stream_t stream);
+
 /* ---- neighbour sampling for mini-batches (BASELINE cfg5; no reference counterpart) -----------
  * For each destination dst_ids[i] (rows of a destination-grouped CSR rowptr/col over n_rows):
  * keep all in-neighbours if deg <= fanout (or fanout < 0), else `fanout` distinct neighbour

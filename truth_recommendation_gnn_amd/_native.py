@@ -191,6 +191,17 @@ _SIGS = {
     "hgnn_score_gather2_planned": (_c_i32, [_c_i32, _p, _c_i64, _p, _c_i32, _p, _p, _p, _p, _p,
                                             _c_i64, _p, ctypes.c_float, _p, _p, _c_i64, _c_i64,
                                             _c_i32, _p, _p, _p, _p, _c_i64, _p, _p, _p]),
+    "hgnn_edge_score_fwd_k_lq": (_c_i32, [_p, _p, _c_i32, _c_i64, _c_i64, _p, _p, _p, _p, _p, _p,
+                                          _c_i32, _c_i64, _p, _p, _p, _p, _p, _p, _p]),
+    "hgnn_edge_score_fwd_k_lq_bf16": (_c_i32, [_p, _p, _c_i32, _c_i64, _c_i64, _p, _p, _p, _p, _p,
+                                               _p, _c_i32, _c_i64, _p, _p, _p, _p, _p, _p, _p]),
+    "hgnn_score_gather2_lq": (_c_i32, [_c_i32, _p, _c_i64, _p, _c_i32, _p, _p, _p, _p, _p, _c_i64,
+                                       _p, ctypes.c_float, _p, _p, _p, _c_i64, _c_i64, _c_i32, _p,
+                                       _p, _p]),
+    "hgnn_score_gather2_planned_lq": (_c_i32, [_c_i32, _p, _c_i64, _p, _c_i32, _p, _p, _p, _p, _p,
+                                               _c_i64, _p, ctypes.c_float, _p, _p, _p, _c_i64,
+                                               _c_i64, _c_i32, _p, _p, _p, _p, _c_i64, _p, _p,
+                                               _p]),
     "hgnn_scale_unless_one": (_c_i32, [_p, _c_i64, _p, _p]),
     "hgnn_linear_fwd_f32": (_c_i32, [_p, _c_i64, _c_i32, _p, _c_i32, _p, _p, _p]),
     "hgnn_linear_dgrad_f32": (_c_i32, [_p, _c_i64, _c_i32, _p, _c_i32, _p, _p]),

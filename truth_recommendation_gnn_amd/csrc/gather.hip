@@ -57,6 +57,9 @@ struct GatherArgs {
   int32_t hot;                 // col holds hot flags in bit 31 (hgnn_hot_cols): two-policy loads
   int32_t bf16;                // x (and rowvec) hold bf16 rows: the XT = uint16_t instantiations
   int32_t zp;                  // x holds zero-packed fp32 rows (zpack.h): the ZP instantiations
+  // the LQ instantiations (hgnn_score_gather2_lq): the logit of an edge of row r is its score less
+  // row_bias[r], for both lists; null otherwise
+  const float* row_bias;
 };
 
 // bit 31 of a col_hot entry: the source row is one of the relation's H most referenced rows
@@ -121,10 +124,13 @@ struct ZpMask {
 // lane that loads col[p], a batch ahead as cnext is (widx / wnext), and is shuffled to its slot
 // where the round's weights are formed, so no round holds a register per row for it; the order
 // of the mask and value loads is unchanged.
-template <int LPR, int UNROLL, bool NT, bool EW = false>
+//
+// LQ: the row's offset rb (one scalar per item, loaded by gather_item beside rv) is subtracted
+// from each dot product before the sigmoid; nothing else moves.
+template <int LPR, int UNROLL, bool NT, bool EW = false, bool LQ = false>
 __device__ __forceinline__ void segment_sum_zp(const GatherArgs& a, const int32_t* col, int score,
                                                int64_t beg, int64_t end, const float4& rv,
-                                               float4& acc) {
+                                               float4& acc, float rb = 0.f) {
   using V = Vec<4>;
   using MK = ZpMask<LPR>;
   constexpr int NS = 64 / LPR;
@@ -184,6 +190,15 @@ __device__ __forceinline__ void segment_sum_zp(const GatherArgs& a, const int32_
         float sdot = 0.f;
         sdot += V::dot(rv, v[u]);
         sdot = slot_sum<LPR>(sdot);
+        if constexpr (LQ) {   // (segment_sum's LQ weights)
+          sdot -= rb;
+          const float tt = exp_neg_abs(sdot);
+          if constexpr (EW)
+            we[u] = -cw * __shfl(widx, (j + u * NS + slot) & 63, 64) * sigmoid_t(-sdot, tt);
+          else
+            we[u] = score == 1 ? -cw * sigmoid_t(-sdot, tt) : cw * sigmoid_t(sdot, tt);
+          continue;
+        }
         const float sg = sigmoid_t(sdot, exp_neg_abs(sdot));
         if constexpr (EW)   // (the weighted list is the positives': mode 1)
           we[u] = cw * __shfl(widx, (j + u * NS + slot) & 63, 64) * (sg - 1.f);
@@ -217,18 +232,22 @@ __device__ __forceinline__ void segment_sum_zp(const GatherArgs& a, const int32_
 // XT: the source table's element type (RowSrc).  A bf16 row is read 16 B per lane, so d = 128 is
 // 16 lanes per row and 4 rows per wave load; its vectors stay packed while in flight and are
 // widened to fp32 where they are summed.  Everything after the load is fp32 either way.
+//
+// LQ with SC (hgnn_score_gather2_lq): the logit is the score less rb, the row's own offset
+// (row_bias[row], loaded once per item by gather_item), for either weight mode; the weights are
+// the scoring pass's LQ expressions, so both passes give an edge one coefficient.
 template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC, bool HOT, typename XT = float,
-          int ZP = 0>
+          int ZP = 0, bool LQ = false>
 __device__ __forceinline__ void segment_sum(const GatherArgs& a, const int32_t* col, int score,
                                             int64_t beg, int64_t end,
                                             const typename Vec<W>::T (&rv)[VPL],
-                                            typename Vec<W>::T (&acc)[VPL]) {
+                                            typename Vec<W>::T (&acc)[VPL], float rb = 0.f) {
   using V = Vec<W>;
   using S = RowSrc<XT, W>;
   if constexpr (ZP != 0) {
     static_assert(SC && !HOT && VPL == 1 && W == 4 && sizeof(XT) == 4,
                   "zero-packed rows: the fp32 score gather at d = 64 / 128");
-    segment_sum_zp<LPR, UNROLL, ZP == 2, HAS_W>(a, col, score, beg, end, rv[0], acc[0]);
+    segment_sum_zp<LPR, UNROLL, ZP == 2, HAS_W, LQ>(a, col, score, beg, end, rv[0], acc[0], rb);
     return;
   }
   constexpr int NS = 64 / LPR;
@@ -280,6 +299,15 @@ __device__ __forceinline__ void segment_sum(const GatherArgs& a, const int32_t* 
 #pragma unroll
           for (int q = 0; q < VPL; ++q) sdot += V::dot(rv[q], S::widen(v[u][q]));
           sdot = slot_sum<LPR>(sdot);
+          if constexpr (LQ) {
+            // the positives' sigmoid(z) - 1 formed as -sigmoid(-z) (the same t, no cancellation):
+            // an offset of log(1/T) puts z near +22, where 1/(1 + t) - 1 is exactly 0 in fp32
+            sdot -= rb;
+            const float tt = exp_neg_abs(sdot);
+            if constexpr (HAS_W) we[u] = -cw * we[u] * sigmoid_t(-sdot, tt);
+            else we[u] = score == 1 ? -cw * sigmoid_t(-sdot, tt) : cw * sigmoid_t(sdot, tt);
+            continue;
+          }
           const float sg = sigmoid_t(sdot, exp_neg_abs(sdot));
           if constexpr (HAS_W) we[u] = cw * we[u] * (sg - 1.f);   // (the positives: mode 1)
           else we[u] = cw * (score == 1 ? sg - 1.f : sg);
@@ -308,7 +336,7 @@ __device__ __forceinline__ void slot_combine(typename Vec<W>::T (&acc)[VPL]) {
 
 // one item (a light row, or a chunk of a heavy row) per wave
 template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC, bool HOT = false,
-          typename XT = float, int ZP = 0>
+          typename XT = float, int ZP = 0, bool LQ = false>
 __device__ __forceinline__ void gather_item(const GatherArgs& a, const int64_t item) {
   using V = Vec<W>;
   using S = RowSrc<XT, W>;
@@ -353,13 +381,15 @@ __device__ __forceinline__ void gather_item(const GatherArgs& a, const int64_t i
                 ? S::widen(S::load(static_cast<const XT*>(a.rowvec) + row * a.d + c))
                 : V::zero();
   }
+  float rb = 0.f;   // LQ: the row's offset, one scalar per item beside its rv
+  if constexpr (LQ) rb = a.row_bias[row];
   if (own)
-    segment_sum<LPR, VPL, W, UNROLL, HAS_W, SC, HOT, XT, ZP>(a, a.col, a.score, beg, end, rv,
-                                                             acc);
+    segment_sum<LPR, VPL, W, UNROLL, HAS_W, SC, HOT, XT, ZP, LQ>(a, a.col, a.score, beg, end, rv,
+                                                                 acc, rb);
   // (the second list carries no per-edge weights: HAS_W stays off for it in a score gather)
   if (two && !partial)
-    segment_sum<LPR, VPL, W, UNROLL, HAS_W && !SC, SC, false, XT, ZP>(
-        a, a.col2, 2, a.rowptr2[row], a.rowptr2[row + 1], rv, acc);
+    segment_sum<LPR, VPL, W, UNROLL, HAS_W && !SC, SC, false, XT, ZP, LQ>(
+        a, a.col2, 2, a.rowptr2[row], a.rowptr2[row + 1], rv, acc, rb);
   slot_combine<LPR, VPL, W>(acc);
   if (!writer) return;
   float s = 1.f;
@@ -383,22 +413,22 @@ __device__ __forceinline__ void gather_item(const GatherArgs& a, const int64_t i
 }
 
 template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC = false, bool HOT = false,
-          typename XT = float>
+          typename XT = float, bool LQ = false>
 __global__ void __launch_bounds__(256) k_gather(const GatherArgs a) {
   const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (item >= a.n_items) return;
-  gather_item<LPR, VPL, W, UNROLL, HAS_W, SC, HOT, XT>(a, item);
+  gather_item<LPR, VPL, W, UNROLL, HAS_W, SC, HOT, XT, 0, LQ>(a, item);
 }
 
 // The ZP gather as its own kernel (ZP = 1, or 2 with nt value loads): it holds a round's loaded
 // words and the next round's masks at once, and left to itself the register allocator spent
 // 112 VGPRs on it (4 waves per SIMD); asked for 6 waves it fits without a spill in the loop.
-template <int LPR, int UNROLL, int ZP, bool EW = false>
+template <int LPR, int UNROLL, int ZP, bool EW = false, bool LQ = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
 k_gather_zp(const GatherArgs a) {
   const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (item >= a.n_items) return;
-  gather_item<LPR, 1, 4, UNROLL, EW, true, false, float, ZP>(a, item);
+  gather_item<LPR, 1, 4, UNROLL, EW, true, false, float, ZP, LQ>(a, item);
 }
 
 // Several gathers of one row width in one launch (hgnn_gather_reduce_multi): job j owns the
@@ -496,7 +526,7 @@ struct NegPlan {
 
 // item: a row, a chunk of a row heavy in its positives (slab), or a chunk of a row heavy in its
 // negatives (NegPlan::slab), in that order
-template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, typename XT, int ZP>
+template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, typename XT, int ZP, bool LQ = false>
 __device__ __forceinline__ void gather_item_pn(const GatherArgs& a, const NegPlan& p,
                                                const int64_t item) {
   using V = Vec<W>;
@@ -548,8 +578,12 @@ __device__ __forceinline__ void gather_item_pn(const GatherArgs& a, const NegPla
     rv[q] = c < a.d ? S::widen(S::load(static_cast<const XT*>(a.rowvec) + row * a.d + c))
                     : V::zero();
   }
-  segment_sum<LPR, VPL, W, UNROLL, HAS_W, true, false, XT, ZP>(a, a.col, 1, beg, end, rv, acc);
-  segment_sum<LPR, VPL, W, UNROLL, false, true, false, XT, ZP>(a, a.col2, 2, beg2, end2, rv, acc);
+  float rb = 0.f;   // LQ: the row's offset, for whichever list (or chunk of one) this item sums
+  if constexpr (LQ) rb = a.row_bias[row];
+  segment_sum<LPR, VPL, W, UNROLL, HAS_W, true, false, XT, ZP, LQ>(a, a.col, 1, beg, end, rv, acc,
+                                                                   rb);
+  segment_sum<LPR, VPL, W, UNROLL, false, true, false, XT, ZP, LQ>(a, a.col2, 2, beg2, end2, rv,
+                                                                   acc, rb);
   slot_combine<LPR, VPL, W>(acc);
   if (!writer) return;
 #pragma unroll
@@ -562,19 +596,19 @@ __device__ __forceinline__ void gather_item_pn(const GatherArgs& a, const NegPla
   }
 }
 
-template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, typename XT>
+template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, typename XT, bool LQ = false>
 __global__ void __launch_bounds__(256) k_gather_pn(const GatherArgs a, const NegPlan p) {
   const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (item >= a.n_items + p.max_chunks) return;
-  gather_item_pn<LPR, VPL, W, UNROLL, HAS_W, XT, 0>(a, p, item);
+  gather_item_pn<LPR, VPL, W, UNROLL, HAS_W, XT, 0, LQ>(a, p, item);
 }
 
-template <int LPR, int UNROLL, int ZP, bool EW>
+template <int LPR, int UNROLL, int ZP, bool EW, bool LQ = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
 k_gather_pn_zp(const GatherArgs a, const NegPlan p) {
   const int64_t item = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (item >= a.n_items + p.max_chunks) return;
-  gather_item_pn<LPR, 1, 4, UNROLL, EW, float, ZP>(a, p, item);
+  gather_item_pn<LPR, 1, 4, UNROLL, EW, float, ZP, LQ>(a, p, item);
 }
 
 // out[row] += sum_k slab[first + k] for the rows heavy in their negatives: k_fixup's slices and
@@ -682,6 +716,15 @@ static int launch_gather(Shape<LPR, VPL, W, UM, UW, US>, const GatherArgs& a, Va
   const dim3 grid((unsigned)cdiv(a.n_items, 4)), block(256);
 #define HGNN_G(U, HAS_W, SC, HOT) \
   hipLaunchKernelGGL((k_gather<LPR, VPL, W, U, HAS_W, SC, HOT, XT>), grid, block, 0, stream, a)
+  if (a.row_bias) {   // the LQ instantiations: the two score variants alone (run_gather's rule)
+    if (v == Variant::kScoreWeighted)
+      hipLaunchKernelGGL((k_gather<LPR, VPL, W, US, true, true, false, XT, true>), grid, block, 0,
+                         stream, a);
+    else
+      hipLaunchKernelGGL((k_gather<LPR, VPL, W, US, false, true, false, XT, true>), grid, block, 0,
+                         stream, a);
+    return check_launch(sizeof(XT) == 2 ? "k_gather(lq, bf16)" : "k_gather(lq)");
+  }
   switch (v) {
     case Variant::kScore: HGNN_G(US, false, true, false); break;
     case Variant::kScoreWeighted: HGNN_G(US, true, true, false); break;   // per-edge weights
@@ -699,12 +742,16 @@ static int launch_gather(Shape<LPR, VPL, W, UM, UW, US>, const GatherArgs& a, Va
 // depths), nothing else (run_score2 alone sets GatherArgs::zp, after its width rule)
 static int launch_gather_zp(const GatherArgs& a, Variant v, hipStream_t stream) {
   const dim3 grid((unsigned)cdiv(a.n_items, 4)), block(256);
-#define HGNN_GZP(LPR, ZP)                                                                  \
-  do {                                                                                     \
-    if (v == Variant::kScoreWeighted)                                                      \
-      hipLaunchKernelGGL((k_gather_zp<LPR, 4, ZP, true>), grid, block, 0, stream, a);      \
-    else                                                                                   \
-      hipLaunchKernelGGL((k_gather_zp<LPR, 4, ZP>), grid, block, 0, stream, a);            \
+#define HGNN_GZP(LPR, ZP)                                                                      \
+  do {                                                                                         \
+    if (a.row_bias && v == Variant::kScoreWeighted)                                            \
+      hipLaunchKernelGGL((k_gather_zp<LPR, 4, ZP, true, true>), grid, block, 0, stream, a);    \
+    else if (a.row_bias)                                                                       \
+      hipLaunchKernelGGL((k_gather_zp<LPR, 4, ZP, false, true>), grid, block, 0, stream, a);   \
+    else if (v == Variant::kScoreWeighted)                                                     \
+      hipLaunchKernelGGL((k_gather_zp<LPR, 4, ZP, true>), grid, block, 0, stream, a);          \
+    else                                                                                       \
+      hipLaunchKernelGGL((k_gather_zp<LPR, 4, ZP>), grid, block, 0, stream, a);                \
   } while (0)
   if (a.d == 64) {
     if (a.nt_load) HGNN_GZP(16, 2); else HGNN_GZP(16, 1);
@@ -821,6 +868,8 @@ static int run_gather(GatherArgs a, int64_t n_x, hipStream_t stream) {
     return fail(HGNN_E_ARG, "score_gather: bad mode/arguments");
   if (a.rowptr2 && a.score != 1)
     return fail(HGNN_E_ARG, "score_gather2: needs mode 1 for the first list");
+  if (a.row_bias && !(a.score == 1 && a.rowptr2))
+    return fail(HGNN_E_ARG, "gather: row_bias belongs to the two-list score gather");
   const Variant v = a.score ? (score_w ? Variant::kScoreWeighted : Variant::kScore)
                     : a.hot ? (has_w ? Variant::kHotWeighted : Variant::kHot)
                             : (has_w ? Variant::kWeighted : Variant::kPlain);
@@ -851,7 +900,7 @@ static int run_score2(const char* who, Rows rows, const void* x, int64_t n_x, co
                       const float* cscale, float inv_e, const int32_t* heavy_rows,
                       const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks, int32_t chunk,
                       float* slab, float* out, hgnn_stream_t stream, bool weighted = false,
-                      const float* edge_w = nullptr) {
+                      const float* edge_w = nullptr, const float* row_bias = nullptr) {
   if (rows == Rows::kBf16)
     if (int rc = bf16_width_rule(d, who)) return rc;
   if (rows == Rows::kZp && !zpack::width_ok(d))
@@ -863,6 +912,7 @@ static int run_score2(const char* who, Rows rows, const void* x, int64_t n_x, co
   score_args(a, rowvec, cscale, inv_e, 1, rowptr_n, col_n);
   a.bf16 = rows == Rows::kBf16;
   a.zp = rows == Rows::kZp;
+  a.row_bias = row_bias;
   return run_gather(a, n_x, as_stream(stream));
 }
 
@@ -871,6 +921,15 @@ static int run_score2(const char* who, Rows rows, const void* x, int64_t n_x, co
 template <typename XT, int LPR, int VPL, int W, int UM, int UW, int US>
 static int launch_gather_pn(Shape<LPR, VPL, W, UM, UW, US>, const GatherArgs& a, const NegPlan& p,
                             bool weighted, dim3 grid, hipStream_t stream) {
+  if (a.row_bias) {   // the LQ instantiations
+    if (weighted)
+      hipLaunchKernelGGL((k_gather_pn<LPR, VPL, W, US, true, XT, true>), grid, dim3(256), 0,
+                         stream, a, p);
+    else
+      hipLaunchKernelGGL((k_gather_pn<LPR, VPL, W, US, false, XT, true>), grid, dim3(256), 0,
+                         stream, a, p);
+    return check_launch(sizeof(XT) == 2 ? "k_gather_pn(lq, bf16)" : "k_gather_pn(lq)");
+  }
   if (weighted)
     hipLaunchKernelGGL((k_gather_pn<LPR, VPL, W, US, true, XT>), grid, dim3(256), 0, stream, a, p);
   else
@@ -882,7 +941,13 @@ static int launch_gather_pn_zp(const GatherArgs& a, const NegPlan& p, bool weigh
                                hipStream_t stream) {
 #define HGNN_GPZ(LPR, ZP)                                                                       \
   do {                                                                                          \
-    if (weighted)                                                                               \
+    if (a.row_bias && weighted)                                                                 \
+      hipLaunchKernelGGL((k_gather_pn_zp<LPR, 4, ZP, true, true>), grid, dim3(256), 0, stream,  \
+                         a, p);                                                                 \
+    else if (a.row_bias)                                                                        \
+      hipLaunchKernelGGL((k_gather_pn_zp<LPR, 4, ZP, false, true>), grid, dim3(256), 0, stream, \
+                         a, p);                                                                 \
+    else if (weighted)                                                                          \
       hipLaunchKernelGGL((k_gather_pn_zp<LPR, 4, ZP, true>), grid, dim3(256), 0, stream, a, p); \
     else                                                                                        \
       hipLaunchKernelGGL((k_gather_pn_zp<LPR, 4, ZP, false>), grid, dim3(256), 0, stream, a, p);\
@@ -902,8 +967,8 @@ static int run_score2_planned(Rows rows, const void* x, int64_t n_x, const void*
                               const float* cscale, float inv_e, const int32_t* heavy_rows,
                               const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
                               int32_t chunk, float* slab, NegPlan p, float* out,
-                              hipStream_t stream) {
-  const char* who = "score_gather2_planned";
+                              hipStream_t stream, const char* who = "score_gather2_planned",
+                              const float* row_bias = nullptr) {
   if (d <= 0 || n_rows < 0 || n_heavy < 0 || chunk <= 0 || p.max_heavy < 0)
     return fail(HGNN_E_ARG, "%s: bad sizes d=%d n_rows=%lld chunk=%d", who, d, (long long)n_rows,
                 chunk);
@@ -923,6 +988,7 @@ static int run_score2_planned(Rows rows, const void* x, int64_t n_x, const void*
   score_args(a, rowvec, cscale, inv_e, 1, rowptr_n, col_n);
   a.bf16 = rows == Rows::kBf16;
   a.zp = rows == Rows::kZp;
+  a.row_bias = row_bias;
   nt_policy(a, n_x, elem_bytes(a));
   const bool weighted = edge_w != nullptr;
   const dim3 grid((unsigned)cdiv(a.n_items + p.max_chunks, 4));
@@ -1196,6 +1262,46 @@ int hgnn_score_gather2_planned(int32_t rows, const void* x, int64_t n_x, const v
   return run_score2_planned(r, x, n_x, rowvec, d, rowptr, col, edge_w, rowptr_n, col_n, n_rows,
                             cscale, inv_e, heavy_rows, heavy_first, n_heavy, n_chunks, chunk, slab,
                             p, out, as_stream(stream));
+}
+
+int hgnn_score_gather2_lq(int32_t rows, const void* x, int64_t n_x, const void* rowvec, int32_t d,
+                          const int32_t* rowptr, const int32_t* col, const float* edge_w,
+                          const int32_t* rowptr_n, const int32_t* col_n, int64_t n_rows,
+                          const float* cscale, float inv_e, const float* row_bias,
+                          const int32_t* heavy_rows, const int32_t* heavy_first, int64_t n_heavy,
+                          int64_t n_chunks, int32_t chunk, float* slab, float* out,
+                          hgnn_stream_t stream) {
+  if (rows < HGNN_ROWS_F32 || rows > HGNN_ROWS_ZP)
+    return fail(HGNN_E_ARG, "score_gather2_lq: rows=%d", rows);
+  if (!row_bias) return fail(HGNN_E_ARG, "score_gather2_lq: row_bias is null");
+  const Rows r = rows == HGNN_ROWS_BF16 ? Rows::kBf16 : rows == HGNN_ROWS_ZP ? Rows::kZp : Rows::kF32;
+  return run_score2("score_gather2_lq", r, x, n_x, rowvec, d, rowptr, col, rowptr_n, col_n, n_rows,
+                    cscale, inv_e, heavy_rows, heavy_first, n_heavy, n_chunks, chunk, slab, out,
+                    stream, false, edge_w, row_bias);
+}
+
+int hgnn_score_gather2_planned_lq(int32_t rows, const void* x, int64_t n_x, const void* rowvec,
+                                  int32_t d, const int32_t* rowptr, const int32_t* col,
+                                  const float* edge_w, const int32_t* rowptr_n,
+                                  const int32_t* col_n, int64_t n_rows, const float* cscale,
+                                  float inv_e, const float* row_bias, const int32_t* heavy_rows,
+                                  const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
+                                  int32_t chunk, float* slab, const int32_t* neg_heavy_rows,
+                                  const int32_t* neg_heavy_first, const int32_t* d_neg_counts2,
+                                  int64_t neg_max_heavy, float* neg_slab, float* out,
+                                  hgnn_stream_t stream) {
+  const char* who = "score_gather2_planned_lq";
+  if (rows < HGNN_ROWS_F32 || rows > HGNN_ROWS_ZP) return fail(HGNN_E_ARG, "%s: rows=%d", who, rows);
+  if (!row_bias) return fail(HGNN_E_ARG, "%s: row_bias is null", who);
+  NegPlan p{};
+  p.heavy_rows = neg_heavy_rows; p.heavy_first = neg_heavy_first; p.counts = d_neg_counts2;
+  p.slab = neg_slab;
+  p.max_heavy = neg_max_heavy;
+  p.max_chunks = 2 * neg_max_heavy;
+  const Rows r = rows == HGNN_ROWS_BF16 ? Rows::kBf16 : rows == HGNN_ROWS_ZP ? Rows::kZp : Rows::kF32;
+  return run_score2_planned(r, x, n_x, rowvec, d, rowptr, col, edge_w, rowptr_n, col_n, n_rows,
+                            cscale, inv_e, heavy_rows, heavy_first, n_heavy, n_chunks, chunk, slab,
+                            p, out, as_stream(stream), who, row_bias);
 }
 
 }  // extern "C"

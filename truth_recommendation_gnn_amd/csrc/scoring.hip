@@ -246,6 +246,7 @@ __global__ void __launch_bounds__(256) k_edge_score(const ScoreArgs a) {
 struct ScoreArgsK {
   ScoreArgs s;
   int32_t n_neg;
+  const float* post_bias;      // LQ: the per-post offset of the logits (fp32 [n_posts]), else null
 };
 
 // One wave per user, U[u] in registers, as k_edge_score.  A 64-edge chunk is walked in sweeps of
@@ -257,7 +258,18 @@ struct ScoreArgsK {
 // 64 * n_neg ids of a chunk being contiguous) are loaded before the previous sweep runs.  An
 // out-of-range id is counted into err and kept as -1: its row load reads post 0 and its weight
 // and loss term are zeroed.  hpos / neg_key / neg_w are not written.
-template <int LPR, int VPL, int W, bool NT = false, typename XT = float, bool EW = false>
+//
+// LQ (hgnn_edge_score_fwd_k_lq): every scored pair's logit is <U[u], P[p]> - post_bias[p].  The
+// lane that holds an edge's id for a sweep loads post_bias[id] where the id becomes available (the
+// positive's with col, a negative's where its sweep checks the id: the 4-byte dependent read is
+// issued ahead of the sweep's first rows and is older than they are, so the first step's wait for
+// its rows covers it); an id kept as -1 reads entry 0, as its row load reads post 0.  The value
+// reaches the scoring slot by the shuffle the id takes and is subtracted from the dot product
+// before exp_neg_abs; the rows, the sums into dU and their order are unchanged.  The one other
+// difference is the positives' coefficient sigmoid(z) - 1, formed as -sigmoid(-z) (score_step).
+// Its own instantiations: with LQ off this is the code it was.
+template <int LPR, int VPL, int W, bool NT = false, typename XT = float, bool EW = false,
+          bool LQ = false>
 __global__ void __launch_bounds__(256) k_edge_score_k(const ScoreArgsK ak) {
   using V = Vec<W>;
   using S = RowSrc<XT, W>;
@@ -295,6 +307,12 @@ __global__ void __launch_bounds__(256) k_edge_score_k(const ScoreArgsK ak) {
         pid = a.col[base + lane];
         if constexpr (EW) pw = a.edge_w[base + lane];
       }
+      // the offset of an id this lane holds (unconditional, as the row loads are: -1 reads entry 0)
+      auto bias_of = [&](int id) -> float {
+        if constexpr (LQ) return ak.post_bias[max(id, 0)];
+        else return 0.f;
+      };
+      const float pq = bias_of(pid);
       // column j of this lane's edge as loaded (or drawn), checked only where its sweep starts:
       // the check waits for the load, the load is issued a sweep ahead
       auto raw_neg = [&](int j) -> int64_t {
@@ -331,8 +349,8 @@ __global__ void __launch_bounds__(256) k_edge_score_k(const ScoreArgsK ak) {
           }
         }
       };
-      auto score_step = [&](auto pos0, auto two, int j, int id0, int id1, const Raw (&r0)[VPL],
-                            const Raw (&r1)[VPL]) {
+      auto score_step = [&](auto pos0, auto two, int j, int id0, int id1, float q0, float q1,
+                            const Raw (&r0)[VPL], const Raw (&r1)[VPL]) {
         const int e = j + slot;
         typename V::T v0[VPL], v1[VPL];
 #pragma unroll
@@ -340,13 +358,22 @@ __global__ void __launch_bounds__(256) k_edge_score_k(const ScoreArgsK ak) {
           v0[q] = S::widen(r0[q]);
           if constexpr (two) v1[q] = S::widen(r1[q]);
         }
-        const float s0 = slot_dot<LPR, VPL, W>(uv, v0);
+        float s0 = slot_dot<LPR, VPL, W>(uv, v0);
         float s1 = 0.f;
         if constexpr (two) s1 = slot_dot<LPR, VPL, W>(uv, v1);
+        if constexpr (LQ) {   // the logit: the score less the row's post's offset
+          s0 -= __shfl(q0, e & 63, 64);
+          if constexpr (two) s1 -= __shfl(q1, e & 63, 64);
+        }
         const float t0 = exp_neg_abs(s0), t1 = exp_neg_abs(s1);
         float h0, h1 = 0.f;
         bool ok0 = e < n, ok1 = e < n;
-        if constexpr (pos0) {
+        if constexpr (pos0 && LQ) {
+          // sigmoid(z) - 1 formed as -sigmoid(-z) from the same t: no cancellation.  An offset of
+          // log(1/T) (a post of weight 0, PostDistribution.log_q) puts z near +22, where
+          // 1/(1 + t) - 1 is exactly 0 in fp32 and the post's positives would push nothing.
+          h0 = -(c * a.inv_e) * sigmoid_t(-s0, t0);
+        } else if constexpr (pos0) {
           h0 = c * a.inv_e * (sigmoid_t(s0, t0) - 1.f);
         } else {
           h0 = a.inv_e * sigmoid_t(s0, t0);
@@ -390,30 +417,35 @@ __global__ void __launch_bounds__(256) k_edge_score_k(const ScoreArgsK ak) {
           if constexpr (two) V::fma(acc[q], h1, v1[q]);
         }
       };
-      auto sweep = [&](auto pos0, auto two, int id0, int id1) {
+      auto sweep = [&](auto pos0, auto two, int id0, int id1, float q0, float q1) {
         load_step(pos0, two, 0, id0, id1, a0, a1);
         for (int j = 0; j < n; j += 2 * NS) {
           load_step(pos0, two, j + NS, id0, id1, b0, b1);
-          score_step(pos0, two, j, id0, id1, a0, a1);
+          score_step(pos0, two, j, id0, id1, q0, q1, a0, a1);
           if (j + NS >= n) break;
           load_step(pos0, two, j + 2 * NS, id0, id1, a0, a1);
-          score_step(pos0, two, j + NS, id0, id1, b0, b1);
+          score_step(pos0, two, j + NS, id0, id1, q0, q1, b0, b1);
         }
       };
       const int nid = checked(raw_neg(0));
+      const float nq = bias_of(nid);
       int j = 1;
       int64_t rw0 = 0, rw1 = 0;
       if (j < K) rw0 = raw_neg(j);
       if (j + 1 < K) rw1 = raw_neg(j + 1);
-      sweep(Yes{}, Yes{}, pid, nid);
+      sweep(Yes{}, Yes{}, pid, nid, pq, nq);
       while (j + 1 < K) {
         const int i0 = checked(rw0), i1 = checked(rw1);
+        const float q0 = bias_of(i0), q1 = bias_of(i1);
         j += 2;
         if (j < K) rw0 = raw_neg(j);
         if (j + 1 < K) rw1 = raw_neg(j + 1);
-        sweep(No{}, Yes{}, i0, i1);
+        sweep(No{}, Yes{}, i0, i1, q0, q1);
       }
-      if (j < K) sweep(No{}, No{}, checked(rw0), 0);
+      if (j < K) {
+        const int i0 = checked(rw0);
+        sweep(No{}, No{}, i0, 0, bias_of(i0), 0.f);
+      }
     }
 #pragma unroll
     for (int m = LPR; m < 64; m <<= 1)
@@ -551,18 +583,30 @@ static bool score_nt_policy(int64_t n_posts, int32_t d, bool bf16) {
   return n_posts * d * (bf16 ? 2 : 4) >= kScoreNtBytes;
 }
 
-template <int LPR, int VPL, int W, typename XT, bool NT, bool EW>
-static int launch_score_k(const ScoreArgs& a, int32_t n_neg, int64_t nblocks, hipStream_t stream) {
-  const ScoreArgsK ak{a, n_neg};
-  hipLaunchKernelGGL((k_edge_score_k<LPR, VPL, W, NT, XT, EW>), dim3((unsigned)nblocks),
+template <int LPR, int VPL, int W, typename XT, bool NT, bool EW, bool LQ = false>
+static int launch_score_k(const ScoreArgs& a, int32_t n_neg, int64_t nblocks, hipStream_t stream,
+                          const float* post_bias = nullptr) {
+  const ScoreArgsK ak{a, n_neg, post_bias};
+  hipLaunchKernelGGL((k_edge_score_k<LPR, VPL, W, NT, XT, EW, LQ>), dim3((unsigned)nblocks),
                      dim3(256), 0, stream, ak);
-  return check_launch("k_edge_score_k");
+  return check_launch(LQ ? "k_edge_score_k(lq)" : "k_edge_score_k");
 }
 
-// n_neg > 0: the k-negative kernel (hgnn_edge_score_fwd_k), under the same two choices
+// n_neg > 0: the k-negative kernel (hgnn_edge_score_fwd_k), under the same two choices;
+// post_bias (with n_neg > 0 only): its LQ instantiations (hgnn_edge_score_fwd_k_lq)
 template <int LPR, int VPL, int W, typename XT = float>
 static int launch_score(const ScoreArgs& a, int64_t nblocks, hipStream_t stream,
-                        int32_t n_neg = 0) {
+                        int32_t n_neg = 0, const float* post_bias = nullptr) {
+  if (n_neg > 0 && post_bias) {
+    const float* b = post_bias;
+    if (a.edge_w)
+      return a.nt_neg
+                 ? launch_score_k<LPR, VPL, W, XT, true, true, true>(a, n_neg, nblocks, stream, b)
+                 : launch_score_k<LPR, VPL, W, XT, false, true, true>(a, n_neg, nblocks, stream, b);
+    return a.nt_neg
+               ? launch_score_k<LPR, VPL, W, XT, true, false, true>(a, n_neg, nblocks, stream, b)
+               : launch_score_k<LPR, VPL, W, XT, false, false, true>(a, n_neg, nblocks, stream, b);
+  }
   if (n_neg > 0) {
     if (a.edge_w)
       return a.nt_neg ? launch_score_k<LPR, VPL, W, XT, true, true>(a, n_neg, nblocks, stream)
@@ -606,7 +650,8 @@ int32_t hgnn_score_nt_policy(int64_t n_posts, int32_t d, int32_t bf16) {
 int32_t hgnn_loss_one_pass(int64_t n_users) { return loss_one_pass(n_users) ? 1 : 0; }
 
 // `bf16`: U and P hold bf16 rows (hgnn_edge_score_fwd_bf16); `edge_w`: the per-edge weights of
-// the _w entries (null: the collapsed weighting, c alone); `n_neg` > 0: the _k entries' kernel
+// the _w entries (null: the collapsed weighting, c alone); `n_neg` > 0: the _k entries' kernel;
+// `post_bias`: the _k_lq entries' offsets (with n_neg > 0)
 static int edge_score_fwd(const void* U, const void* P, int32_t d, int64_t n_users,
                           int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
                           const int64_t* neg_u_order, const int32_t* neg32,
@@ -614,7 +659,8 @@ static int edge_score_fwd(const void* U, const void* P, int32_t d, int64_t n_use
                           float* dU, float* hpos, int32_t* neg_key, int32_t* neg_user,
                           float* neg_w, float* part, float* loss, int32_t* err,
                           hgnn_stream_t stream_, bool bf16 = false,
-                          const float* edge_w = nullptr, int32_t n_neg = 0) {
+                          const float* edge_w = nullptr, int32_t n_neg = 0,
+                          const float* post_bias = nullptr) {
   hipStream_t stream = as_stream(stream_);
   if (d < 1 || n_users < 0 || n_posts < 0 || n_edges < 0)
     return fail(HGNN_E_ARG, "edge_score: bad sizes");
@@ -637,16 +683,16 @@ static int edge_score_fwd(const void* U, const void* P, int32_t d, int64_t n_use
     // measured slower: users average ~20 edges, so wider steps waste the tail)
     if (bf16) {   // 16 B = 8 elements per lane: d = 128 is 16 lanes per row, 4 edges per step
       using B = uint16_t;
-      if (d <= 64) rc = launch_score<8, 1, 8, B>(a, nb, stream, n_neg);
-      else if (d <= 128) rc = launch_score<16, 1, 8, B>(a, nb, stream, n_neg);
-      else if (d <= 256) rc = launch_score<32, 1, 8, B>(a, nb, stream, n_neg);
-      else rc = launch_score<64, 1, 8, B>(a, nb, stream, n_neg);
+      if (d <= 64) rc = launch_score<8, 1, 8, B>(a, nb, stream, n_neg, post_bias);
+      else if (d <= 128) rc = launch_score<16, 1, 8, B>(a, nb, stream, n_neg, post_bias);
+      else if (d <= 256) rc = launch_score<32, 1, 8, B>(a, nb, stream, n_neg, post_bias);
+      else rc = launch_score<64, 1, 8, B>(a, nb, stream, n_neg, post_bias);
     }
-    else if (d % 4 == 0 && d <= 64) rc = launch_score<16, 1, 4>(a, nb, stream, n_neg);
-    else if (d % 4 == 0 && d <= 128) rc = launch_score<32, 1, 4>(a, nb, stream, n_neg);
-    else if (d % 4 == 0 && d <= 256) rc = launch_score<64, 1, 4>(a, nb, stream, n_neg);
-    else if (d <= 64) rc = launch_score<64, 1, 1>(a, nb, stream, n_neg);
-    else if (d <= 512) rc = launch_score<64, 8, 1>(a, nb, stream, n_neg);
+    else if (d % 4 == 0 && d <= 64) rc = launch_score<16, 1, 4>(a, nb, stream, n_neg, post_bias);
+    else if (d % 4 == 0 && d <= 128) rc = launch_score<32, 1, 4>(a, nb, stream, n_neg, post_bias);
+    else if (d % 4 == 0 && d <= 256) rc = launch_score<64, 1, 4>(a, nb, stream, n_neg, post_bias);
+    else if (d <= 64) rc = launch_score<64, 1, 1>(a, nb, stream, n_neg, post_bias);
+    else if (d <= 512) rc = launch_score<64, 8, 1>(a, nb, stream, n_neg, post_bias);
     else return fail(HGNN_E_UNSUPPORTED, "edge_score: d=%d", d);
     if (rc) return rc;
   }
@@ -772,7 +818,8 @@ static int edge_score_fwd_k(const char* who, bool bf16, const void* U, const voi
                             const int32_t* col_u, const float* edge_w, const int64_t* neg_i64,
                             const int32_t* neg_i32, const uint64_t* d_seed, int32_t n_neg,
                             int64_t n_edges, const float* cscale, float* dU, float* part,
-                            float* loss, int32_t* err, hgnn_stream_t stream) {
+                            float* loss, int32_t* err, hgnn_stream_t stream,
+                            const float* post_bias = nullptr) {
   if (n_neg < 1) return fail(HGNN_E_ARG, "%s: n_neg=%d (at least one negative per edge)", who,
                              n_neg);
   if (bf16 && d > 0 && (d % 8 != 0 || d > 512))
@@ -788,7 +835,7 @@ static int edge_score_fwd_k(const char* who, bool bf16, const void* U, const voi
                 (long long)n_posts);
   return edge_score_fwd(U, P, d, n_users, n_posts, rowptr_u, col_u, neg_i64, neg_i32, d_seed,
                         nullptr, n_edges, cscale, dU, nullptr, nullptr, nullptr, nullptr, part,
-                        loss, err, stream, bf16, edge_w, n_neg);
+                        loss, err, stream, bf16, edge_w, n_neg, post_bias);
 }
 
 int hgnn_edge_score_fwd_k(const float* U, const float* P, int32_t d, int64_t n_users,
@@ -811,6 +858,32 @@ int hgnn_edge_score_fwd_k_bf16(const uint16_t* U, const uint16_t* P, int32_t d, 
   return edge_score_fwd_k("edge_score_fwd_k_bf16", true, U, P, d, n_users, n_posts, rowptr_u,
                           col_u, edge_w, neg_i64, neg_i32, d_seed, n_neg, n_edges, cscale, dU,
                           part, loss, err, stream);
+}
+
+// The logQ entries: post_bias's own rule, then those of the _k entries under this entry's name.
+int hgnn_edge_score_fwd_k_lq(const float* U, const float* P, int32_t d, int64_t n_users,
+                             int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
+                             const float* edge_w, const int64_t* neg_i64, const int32_t* neg_i32,
+                             const uint64_t* d_seed, int32_t n_neg, int64_t n_edges,
+                             const float* cscale, const float* post_bias, float* dU, float* part,
+                             float* loss, int32_t* err, hgnn_stream_t stream) {
+  if (!post_bias) return fail(HGNN_E_ARG, "edge_score_fwd_k_lq: post_bias is null");
+  return edge_score_fwd_k("edge_score_fwd_k_lq", false, U, P, d, n_users, n_posts, rowptr_u,
+                          col_u, edge_w, neg_i64, neg_i32, d_seed, n_neg, n_edges, cscale, dU,
+                          part, loss, err, stream, post_bias);
+}
+
+int hgnn_edge_score_fwd_k_lq_bf16(const uint16_t* U, const uint16_t* P, int32_t d,
+                                  int64_t n_users, int64_t n_posts, const int32_t* rowptr_u,
+                                  const int32_t* col_u, const float* edge_w,
+                                  const int64_t* neg_i64, const int32_t* neg_i32,
+                                  const uint64_t* d_seed, int32_t n_neg, int64_t n_edges,
+                                  const float* cscale, const float* post_bias, float* dU,
+                                  float* part, float* loss, int32_t* err, hgnn_stream_t stream) {
+  if (!post_bias) return fail(HGNN_E_ARG, "edge_score_fwd_k_lq_bf16: post_bias is null");
+  return edge_score_fwd_k("edge_score_fwd_k_lq_bf16", true, U, P, d, n_users, n_posts, rowptr_u,
+                          col_u, edge_w, neg_i64, neg_i32, d_seed, n_neg, n_edges, cscale, dU,
+                          part, loss, err, stream, post_bias);
 }
 
 // Uniform draws in [0, hi): out[i] = hi * (splitmix64(seed + i * golden) >> 32) >> 32 (Lemire's

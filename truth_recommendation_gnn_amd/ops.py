@@ -618,10 +618,11 @@ def _plan_negatives(rowptr_n: torch.Tensor, n_posts: int, n_pairs: int, chunk: i
 
 
 def _score_gather2_planned(U, P, pos, negs, cscale, inv_e, out, Uz, edge_w, plan: _NegPlan,
-                           pplan: _PlanArgs, nb, cb):
+                           pplan: _PlanArgs, nb, cb, row_bias=None):
     """``_score_gather2`` through ``hgnn_score_gather2_planned``: the negatives' heavy lists go
     chunk by chunk into a slab of their own, ``2 * max_heavy`` rows of d floats (the bound on the
-    chunks; at 200M pairs, chunk 1024 and d = 128 that is 200 MB), allocated per call."""
+    chunks; at 200M pairs, chunk 1024 and d = 128 that is 200 MB), allocated per call.
+    ``row_bias``: ``hgnn_score_gather2_planned_lq``."""
     dev = out.device
     d = int(out.shape[1])
     n = pos.n_rows
@@ -629,22 +630,26 @@ def _score_gather2_planned(U, P, pos, negs, cscale, inv_e, out, Uz, edge_w, plan
         raise ValueError("edge_bce_loss: the negatives' plan was made for another chunk")
     rows, table = ((1, U) if U.dtype == torch.bfloat16 else (2, Uz) if Uz is not None else (0, U))
     neg_slab = torch.empty(max(2 * plan.max_heavy, 1) * d, dtype=torch.float32, device=dev)
+    entry = "hgnn_score_gather2_planned" + ("_lq" if row_bias is not None else "")
+    bias = (N.ptr(row_bias),) if row_bias is not None else ()
     with _timed(f"score_gather_planned[{n}<-{U.shape[0]}]x{d}", nb, cb):
-        N.check(N.lib().hgnn_score_gather2_planned(
+        N.check(getattr(N.lib(), entry)(
             rows, N.ptr(table), U.shape[0], N.ptr(P), d, N.ptr(pos.rowptr), N.ptr(pos.col),
-            N.ptr(edge_w), N.ptr(negs.rowptr), N.ptr(negs.col), n, N.ptr(cscale), inv_e, *pplan,
-            N.ptr(plan.heavy_rows), N.ptr(plan.heavy_first), N.ptr(plan.counts), plan.max_heavy,
-            N.ptr(neg_slab), N.ptr(out), N.stream_ptr(dev)), "hgnn_score_gather2_planned")
+            N.ptr(edge_w), N.ptr(negs.rowptr), N.ptr(negs.col), n, N.ptr(cscale), inv_e, *bias,
+            *pplan, N.ptr(plan.heavy_rows), N.ptr(plan.heavy_first), N.ptr(plan.counts),
+            plan.max_heavy, N.ptr(neg_slab), N.ptr(out), N.stream_ptr(dev)), entry)
 
 
-def _score_gather2(U, P, pos, negs, cscale, inv_e, out, Uz=None, edge_w=None, neg_plan=None):
+def _score_gather2(U, P, pos, negs, cscale, inv_e, out, Uz=None, edge_w=None, neg_plan=None,
+                   row_bias=None):
     """Both dP gathers in one pass (hgnn_score_gather2): row r sums its positive edges (mode 1,
     heavy-row plan) and its negatives (mode 2) into one accumulator and writes dP[r] once.
     ``Uz``: ``zpack_rows(U)``; the gather then reads the packed rows (same sums, bit for bit;
     the timer entry keeps its name and the unpacked table's algorithmic bytes).  ``edge_w``: the
     positives' per-edge weights by position of ``pos`` (the ``_w`` entries; 4 B more per
     positive edge).  ``neg_plan``: the ``_NegPlan`` of ``SkewedNegatives``; the gather is then
-    ``hgnn_score_gather2_planned``."""
+    ``hgnn_score_gather2_planned``.  ``row_bias``: the logQ table (fp32 ``[n]``): the ``_lq``
+    entries, each row's offset subtracted from its scores (4 B more per output row)."""
     dev = out.device
     d = int(out.shape[1])
     n = pos.n_rows
@@ -652,11 +657,20 @@ def _score_gather2(U, P, pos, negs, cscale, inv_e, out, Uz=None, edge_w=None, ne
     E = int(pos.col.numel()) + int(negs.col.numel())
     rb = _row_bytes(U)      # U's rows per edge and P's own row per output row
     wb = 4 * int(pos.col.numel()) if edge_w is not None else 0
+    wb += 4 * n if row_bias is not None else 0
     nb = gather_bytes(E, n, d, False, rb) + 4 * (n + 1) + n * rb + wb
     cb = gather_compulsory_bytes(E, n, int(U.shape[0]), d, False, rb) + 4 * (n + 1) + n * rb + wb
     if neg_plan is not None:
         _score_gather2_planned(U, P, pos, negs, cscale, inv_e, out, Uz, edge_w, neg_plan, plan,
-                               nb, cb)
+                               nb, cb, row_bias)
+        return
+    if row_bias is not None:   # one entry for the three row formats, edge_w nullable
+        fmt, table = ((1, U) if U.dtype == torch.bfloat16 else (2, Uz) if Uz is not None else (0, U))
+        with _timed(f"score_gather[{n}<-{U.shape[0]}]x{d}", nb, cb):
+            N.check(N.lib().hgnn_score_gather2_lq(
+                fmt, N.ptr(table), U.shape[0], N.ptr(P), d, N.ptr(pos.rowptr), N.ptr(pos.col),
+                N.ptr(edge_w), N.ptr(negs.rowptr), N.ptr(negs.col), n, N.ptr(cscale), inv_e,
+                N.ptr(row_bias), *plan, N.ptr(out), N.stream_ptr(dev)), "hgnn_score_gather2_lq")
         return
     # the entry point by the rows it reads: bf16, zero-packed fp32, fp32
     rows, table = (("_bf16", U) if U.dtype == torch.bfloat16 else
@@ -1628,7 +1642,7 @@ def _weighting_value(v: str, who: str) -> str:
 
 def link_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: torch.Tensor,
               neg_p: torch.Tensor, pos_weights: torch.Tensor,
-              weighting: str = "mean") -> torch.Tensor:
+              weighting: str = "mean", logq: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The reference training loss (train_gnn.py:259-281), on the device with torch ops.
 
     ``weighting="mean"``: ``BCEWithLogitsLoss()`` has mean reduction, so
@@ -1642,10 +1656,17 @@ def link_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: torch.T
 
     ``SkewedNegatives`` carry no order of their own here: pass their ``.values``, row e being the
     negatives of ``pos_edges[:, e]`` (for :func:`sample_negatives`' user-grouped draws, with the
-    edges in that order)."""
+    edges in that order).
+
+    ``logq`` (floating ``[num_posts]``, e.g. :meth:`PostDistribution.log_q`): the logQ correction,
+    every score less its post's entry (``pos_scores - logq[pos_p]``, ``neg_scores -
+    logq[neg_p]``); a constant, no gradient flows into it.  Without it this is the function it
+    was."""
     _weighting_value(weighting, "link_loss")
     if isinstance(neg_p, SkewedNegatives):
         raise TypeError("link_loss: pass SkewedNegatives.values, in the order of pos_edges")
+    if logq is not None:
+        _logq_rules(logq, int(post_emb.shape[0]), "link_loss")
     pos_u, pos_p = pos_edges[0], pos_edges[1]
     u = user_emb[pos_u]
     pos_scores = (u * post_emb[pos_p]).sum(dim=1)
@@ -1655,6 +1676,10 @@ def link_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: torch.T
         neg_scores = (u[:, None, :] * post_emb[neg_p]).sum(dim=-1)
     else:
         neg_scores = (u * post_emb[neg_p]).sum(dim=1)
+    if logq is not None:
+        b = logq.detach().to(pos_scores.dtype)
+        pos_scores = pos_scores - b[pos_p]
+        neg_scores = neg_scores - b[neg_p]
     crit = torch.nn.functional.binary_cross_entropy_with_logits
     neg_loss = crit(neg_scores, torch.zeros_like(neg_scores))
     if weighting == "edge":
@@ -1722,6 +1747,40 @@ def _edge_weighting(who: str, weighting: str, pos_weights, n_edges: int, clashes
         raise ValueError(f"{who}: weighting='edge' needs pos_weights of shape [{n_edges}], one "
                          "per positive edge in COO order")
     return True
+
+
+def _logq_rules(logq, n_posts: int, who: str, sharded=None) -> None:
+    """The ``logq`` argument checked before anything touches the device: a floating tensor of
+    shape ``[n_posts]``.  ``sharded``: {argument name: value} of the sharded step's arguments,
+    which it does not combine with (each None when not given)."""
+    if not isinstance(logq, torch.Tensor) or not logq.is_floating_point():
+        raise ValueError(f"{who}: logq must be a floating tensor of shape [{n_posts}] "
+                         f"(got {getattr(logq, 'dtype', type(logq).__name__)})")
+    if tuple(logq.shape) != (n_posts,):
+        raise ValueError(f"{who}: logq of shape {list(logq.shape)}; expected [{n_posts}], one "
+                         "entry per post")
+    given = [a for a, v in (sharded or {}).items() if v is not None]
+    if given:
+        raise ValueError(f"{who}: logq does not combine with {' / '.join(given)} (the sharded "
+                         "step stays on the uncorrected scores)")
+
+
+def logq_table(csr: RelationCSR, logq: torch.Tensor) -> torch.Tensor:
+    """``logq`` as the table the two loss kernels read: detached, contiguous fp32, and checked
+    finite — once per tensor object and ``_version``, kept on the ``RelationCSR`` the way
+    :func:`edge_weights_in_kernel_order` keeps the weights (held weakly, compared with ``is``).
+    The finite check is the one host sync, paid when the table is first seen or has changed in
+    place, never per step."""
+    hit = getattr(csr, "_logq", None)
+    if hit is not None and hit[0]() is logq and hit[1] == logq._version:
+        return hit[2]
+    N.require_device(logq)
+    t = logq.detach().to(torch.float32).contiguous()
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError("edge_bce_loss: logq must be finite (a post of weight 0 has no log; "
+                         "PostDistribution.log_q gives it the smallest drawable weight's)")
+    csr._logq = (weakref.ref(logq), logq._version, t)
+    return t
 
 
 def negatives_in_user_order(csr: RelationCSR, neg_p: torch.Tensor) -> torch.Tensor:
@@ -1909,7 +1968,7 @@ def presort_negatives(n_users: int, n_posts: int, pos_edges: torch.Tensor, neg_p
 
 
 def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total: int,
-              ready=None, on_dP=None, p_chunks=None, presorted=None, edge_w=None):
+              ready=None, on_dP=None, p_chunks=None, presorted=None, edge_w=None, logq=None):
     """Loss value and its gradients for a unit upstream gradient: (loss, dU, dP).  ``on_dP(dP)``,
     if given, is called once dP's kernels are enqueued and before the scoring pass (dU, the loss)
     is: the sharded step starts dP's reduce-scatter there, under the scoring pass.
@@ -1929,13 +1988,20 @@ def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total:
 
     ``neg_u_order`` of shape ``[E, k]`` (or a ``NegativeDraw`` made for k): k negatives per
     positive edge, row p those of user-grouped position p; ``n_total`` and ``cscale`` are given as
-    for one negative and scaled here.  Not with the sharded step's arguments either."""
+    for one negative and scaled here.  Not with the sharded step's arguments either.
+
+    ``logq``: the table of :func:`logq_table` (fp32 ``[num_posts]``, or None): both passes then
+    run their ``_lq`` entries, every logit its score less the post's entry.  Not with the sharded
+    step's arguments."""
     sharded = ready is not None or on_dP is not None or p_chunks is not None
+    if logq is not None and sharded:
+        raise ValueError("edge_bce_loss: logq does not combine with ready / on_dP / p_chunks "
+                         "(the sharded step stays on the uncorrected scores)")
     if edge_w is not None and sharded:
         raise ValueError("edge_bce_loss: weighting='edge' does not combine with ready / on_dP / "
                          "p_chunks (the sharded step keeps the scalar cscale)")
     U, P, relu_out = _loss_tables(U, P, csr, sharded)
-    dev = N.require_device(U, P, neg_u_order)
+    dev = N.require_device(U, P, neg_u_order, logq)
     np_, E = P.shape[0], csr.num_edges
     if E == 0:
         # a shard without positive edges (parallel.py): its share of the loss and gradients is
@@ -1963,13 +2029,13 @@ def _edge_bce(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total:
         n_total, c = n_total * negs.k, c * float(negs.k)
     inv_e = 1.0 / n_total if n_total > 0 else 0.0
     dP = _loss_dP(U, P, csr, negs, c, inv_e, err, relu_out, ready, p_chunks, presorted,
-                  edge_w.by_post if edge_w is not None else None)
+                  edge_w.by_post if edge_w is not None else None, logq)
     if on_dP is not None:
         on_dP(dP)
     if ready is not None and p_chunks is not None:
         ready()                                 # all of P, for the scoring pass
     loss, dU = _loss_scoring_pass(U, P, csr, negs, c, n_total, err if check else None,
-                                  edge_w.by_user if edge_w is not None else None)
+                                  edge_w.by_user if edge_w is not None else None, logq)
     if check and int(err[0]):
         raise ValueError("edge_bce_loss: negative post id out of range")
     return loss, dU, dP
@@ -1994,11 +2060,12 @@ def _loss_tables(U, P, csr: RelationCSR, sharded: bool):
 
 
 def _loss_dP(U, P, csr: RelationCSR, negs: _Negatives, c, inv_e, err, relu_out: bool, ready,
-             p_chunks, presorted, edge_w=None) -> torch.Tensor:
+             p_chunks, presorted, edge_w=None, logq=None) -> torch.Tensor:
     """The dP chain: sort the negatives (post, user) by post, then both dP gathers in one pass,
     each edge's weight recomputed from <U[u], P[post]> (hgnn_score_gather2); the scoring pass
     (loss + dU) needs none of it.  ``ready`` / ``p_chunks``: see ``_edge_bce``.  ``edge_w``: the
-    positives' weights in the post-grouped order (never with ``p_chunks``)."""
+    positives' weights in the post-grouped order (never with ``p_chunks``).  ``logq``: the fp32
+    table, one offset per output row (never with ``ready`` / ``p_chunks``)."""
     from .graph import NO_SPLIT, GroupedEdges, Plan
     dev = U.device
     np_, E, pf = P.shape[0], csr.num_edges, csr.fwd
@@ -2036,14 +2103,15 @@ def _loss_dP(U, P, csr: RelationCSR, negs: _Negatives, c, inv_e, err, relu_out: 
     if U.dtype != torch.bfloat16 and ready is None and zpack_on(U, relu_out):
         Uz = zpack_rows(U)
     _score_gather2(U, P, pf, GroupedEdges(rowptr_n, nu_s, nu_s, no_plan, np_), c, inv_e, dP, Uz,
-                   edge_w, neg_plan)
+                   edge_w, neg_plan, logq)
     return dP
 
 
 def _loss_scoring_pass(U, P, csr: RelationCSR, negs: _Negatives, c, n_total: int, err,
-                       edge_w=None):
+                       edge_w=None, logq=None):
     """``(loss, dU)``; ``err``: where it counts out-of-range negatives, or None; ``edge_w``: the
-    positives' weights in the user-grouped order (the ``_w`` entries)."""
+    positives' weights in the user-grouped order (the ``_w`` entries); ``logq``: the fp32 table
+    (the ``_k_lq`` entries, for any k: the k kernel at k = 1 gives the one-negative results)."""
     # (The scoring pass takes no col_hot: with the positives' cold rows read nt it measured
     # 29-33 ms against 25.4 at cfg4 for every H tried, DESIGN §5.)
     dev = U.device
@@ -2058,8 +2126,17 @@ def _loss_scoring_pass(U, P, csr: RelationCSR, negs: _Negatives, c, n_total: int
     # its own row in and a dU row out
     rb, k = _row_bytes(U), negs.k
     wb = 4 * E if edge_w is not None else 0
+    wb += 4 * E * (1 + k) if logq is not None else 0      # one offset per scored pair
     with _timed(f"edge_score_d{d}", E * ((1 + k) * rb + 4 + 8 * k) + nu * (rb + 4 * d) + wb):
-        if k >= 2:
+        if logq is not None:
+            # (k = 1: n_total and c are unscaled, which is the convention at n_neg = 1)
+            entry = ("hgnn_edge_score_fwd_k_lq_bf16" if U.dtype == torch.bfloat16
+                     else "hgnn_edge_score_fwd_k_lq")
+            N.check(getattr(lib, entry)(
+                *head, N.ptr(edge_w), N.ptr(negs.i64), N.ptr(negs.i32),
+                N.ptr(negs.draw.seed if negs.draw is not None else None), k, n_total, N.ptr(c),
+                N.ptr(logq), N.ptr(dU), *tail), entry)
+        elif k >= 2:
             # (n_total and c come scaled by k from _edge_bce: hgnn.h's convention)
             entry = ("hgnn_edge_score_fwd_k_bf16" if U.dtype == torch.bfloat16
                      else "hgnn_edge_score_fwd_k")
@@ -2107,18 +2184,19 @@ class _EdgeBCELoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, n_total: int,
-                ready=None, presorted=None, bf16: bool = False, edge_w=None):
+                ready=None, presorted=None, bf16: bool = False, edge_w=None, logq=None):
         if bf16:
             # bf16 row mode: both passes read the bf16 copies, and those (half the bytes) are
             # what stays saved for the retained-graph recompute instead of U and P
             U, P = rows_to_bf16(U), rows_to_bf16(P)
         loss, dU, dP = _edge_bce(U, P, csr, neg_u_order, cscale, check, n_total, ready,
-                                 presorted=presorted, edge_w=edge_w)
+                                 presorted=presorted, edge_w=edge_w, logq=logq)
         ctx.grads = (dU, dP)
         ctx.save_for_backward(U, P)
         # (edge_w: the weights as this forward read them, in kernel order; a later in-place
-        # change of the caller's tensor builds new ones and leaves these alone)
-        ctx.args = (csr, neg_u_order, cscale, n_total, edge_w)
+        # change of the caller's tensor builds new ones and leaves these alone; logq: the fp32
+        # table of logq_table, kept the same way)
+        ctx.args = (csr, neg_u_order, cscale, n_total, edge_w, logq)
         return loss
 
     @staticmethod
@@ -2126,8 +2204,9 @@ class _EdgeBCELoss(torch.autograd.Function):
     def backward(ctx, go):
         if ctx.grads is None:        # retained graph, second backward: recompute
             U, P = ctx.saved_tensors
-            csr, neg_u_order, cscale, n_total, edge_w = ctx.args
-            _, dU, dP = _edge_bce(U, P, csr, neg_u_order, cscale, False, n_total, edge_w=edge_w)
+            csr, neg_u_order, cscale, n_total, edge_w, logq = ctx.args
+            _, dU, dP = _edge_bce(U, P, csr, neg_u_order, cscale, False, n_total, edge_w=edge_w,
+                                  logq=logq)
         else:
             dU, dP = ctx.grads
             ctx.grads = None         # handed on: autograd may accumulate into them from here
@@ -2137,7 +2216,7 @@ class _EdgeBCELoss(torch.autograd.Function):
             for t in (dU, dP):   # in place; a no-op launch for loss.backward()'s gradient of 1
                 N.check(lib.hgnn_scale_unless_one(N.ptr(t), t.numel(), N.ptr(g), s),
                         "hgnn_scale_unless_one")
-        return dU, dP, None, None, None, None, None, None, None, None, None
+        return dU, dP, None, None, None, None, None, None, None, None, None, None
 
 
 # A tensor carrying this attribute (set True) is a gradient of exactly 1 that nobody writes:
@@ -2160,7 +2239,8 @@ def edge_bce_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: tor
                   n_edges_total: Optional[int] = None,
                   cscale: Optional[torch.Tensor] = None, ready=None,
                   presorted: Optional["PresortedNegatives"] = None,
-                  row_dtype: Optional[str] = None, weighting: str = "mean") -> torch.Tensor:
+                  row_dtype: Optional[str] = None, weighting: str = "mean",
+                  logq: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Fused HIP version of :func:`link_loss` (same value, same gradients).
 
     ``weighting``: "mean" (the default) is the reference's arithmetic, the weights collapsed to
@@ -2202,7 +2282,22 @@ def edge_bce_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: tor
     ``row_dtype``: "fp32", "bf16" or None for ``ROW_DTYPE``.  With "bf16" both passes read bf16
     copies of the two tables (``_edge_bce``); the gradients pass straight through the rounding.
     A width that is no multiple of 8 keeps fp32 rows, and so does the sharded path (``ready``)
-    under ``ROW_DTYPE`` — asking for "bf16" explicitly together with ``ready`` is an error."""
+    under ``ROW_DTYPE`` — asking for "bf16" explicitly together with ``ready`` is an error.
+
+    ``logq`` (floating ``[num_posts]`` on the tables' device, a constant: no gradient into it):
+    the logQ correction of sampled losses.  Every scored pair, positive and negative alike, uses
+    the logit ``<U[u], P[p]> - logq[p]`` in its loss term and its gradient coefficient, inside the
+    same two kernels (``hgnn_edge_score_fwd_k_lq``, ``hgnn_score_gather2*_lq``): the scales, the
+    sums, their order and determinism are unchanged.  :meth:`PostDistribution.log_q` gives
+    ``log(k Q(p))`` for negatives drawn from it.  The tensor is detached, cast to contiguous fp32
+    and checked finite once per tensor object and version (:func:`logq_table`; that check is the
+    one host sync, not repeated per step); a wrong shape, a non-floating dtype or a non-finite
+    entry is a ``ValueError``.  It combines with every form of negatives, k >= 1, both
+    weightings, ``row_dtype="bf16"`` (the table stays fp32), ``HGNN_ZPACK``, ``presorted``
+    (which does not depend on it), ``check`` and ``n_edges_total`` / ``cscale``; with ``ready``
+    it is an error.  ``None`` runs exactly the code it ran before."""
+    if logq is not None:
+        _logq_rules(logq, int(post_emb.shape[0]), "edge_bce_loss", {"ready": ready})
     per_edge = _edge_weighting("edge_bce_loss", weighting, pos_weights, int(pos_edges.shape[1]),
                                {"cscale": cscale, "n_edges_total": n_edges_total,
                                 "ready": ready})
@@ -2230,8 +2325,9 @@ def edge_bce_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: tor
     if bf16:
         _check_f32(user_emb, "edge_bce_loss user_emb")
         _check_f32(post_emb, "edge_bce_loss post_emb")
+    table = logq_table(csr, logq) if logq is not None else None
     return _EdgeBCELoss.apply(user_emb, post_emb, csr, neg_u, cscale, check, n_total, ready,
-                              presorted, bf16, edge_w)
+                              presorted, bf16, edge_w, table)
 
 
 def edge_bce_loss_raw(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: torch.Tensor,
@@ -2239,7 +2335,8 @@ def edge_bce_loss_raw(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges:
                       cscale: Optional[torch.Tensor],
                       neg_order: str = "user", ready=None, on_dP=None, p_chunks=None,
                       presorted: Optional[PresortedNegatives] = None, row_dtype: str = "fp32",
-                      pos_weights: Optional[torch.Tensor] = None, weighting: str = "mean"):
+                      pos_weights: Optional[torch.Tensor] = None, weighting: str = "mean",
+                      logq: Optional[torch.Tensor] = None):
     """:func:`edge_bce_loss` outside autograd: (loss, dL/dU, dL/dP) from the same kernels, for
     callers that run their own backward schedule (``parallel.UserShard.step``; ``on_dP``,
     ``p_chunks``: see ``_edge_bce``; ``presorted``: from :func:`presort_negatives` on the same
@@ -2255,7 +2352,13 @@ def edge_bce_loss_raw(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges:
     ``neg_p`` of shape ``[E, k]``: :func:`edge_bce_loss`'s k negatives per positive edge
     (``n_edges_total`` stays the number of positive edges); with k >= 2, ``ready`` / ``on_dP`` /
     ``p_chunks`` are errors.  A :class:`SkewedNegatives` (``neg_order="user"``): the planned dP
-    gather, as in :func:`edge_bce_loss`; ``ready`` / ``on_dP`` / ``p_chunks`` are errors."""
+    gather, as in :func:`edge_bce_loss`; ``ready`` / ``on_dP`` / ``p_chunks`` are errors.
+
+    ``logq``: :func:`edge_bce_loss`'s logQ table and its rules; with ``ready`` / ``on_dP`` /
+    ``p_chunks`` it is an error, never a fallback to the uncorrected scores."""
+    if logq is not None:
+        _logq_rules(logq, int(post_emb.shape[0]), "edge_bce_loss_raw",
+                    {"ready": ready, "on_dP": on_dP, "p_chunks": p_chunks})
     per_edge = _edge_weighting("edge_bce_loss_raw", weighting, pos_weights,
                                int(pos_edges.shape[1]),
                                {"cscale": cscale, "n_edges_total": n_edges_total, "ready": ready,
@@ -2281,8 +2384,9 @@ def edge_bce_loss_raw(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges:
     if per_edge:
         edge_w = edge_weights_in_kernel_order(csr, pos_weights)
         cscale, n_edges_total = edge_w.one, csr.num_edges
+    table = logq_table(csr, logq) if logq is not None else None
     return _edge_bce(user_emb, post_emb, csr, neg_u, cscale, False, int(n_edges_total), ready,
-                     on_dP, p_chunks, presorted, edge_w)
+                     on_dP, p_chunks, presorted, edge_w, table)
 
 
 def _negatives_user_order(csr, neg_p, neg_order):
@@ -2440,6 +2544,23 @@ class PostDistribution:
         if deg.numel() != int(num_posts):
             raise ValueError(f"PostDistribution.from_degree: a post index of {num_posts} or more")
         return cls(deg.double() ** float(power))
+
+    def log_q(self, num_neg: int = 1) -> torch.Tensor:
+        """The logQ table of this distribution for ``num_neg`` negatives per positive edge, as
+        the ``logq=`` of the loss entry points: fp32 ``[num_posts]`` on the distribution's device,
+        ``log(num_neg * max(q[j], 1) / T)`` computed in float64 from ``q`` and ``T`` and then
+        cast — NCE's ``log(k Q(p))``.  A post of weight 0 is never drawn as a negative but may be
+        a positive, and ``log 0`` would make its logit infinite: it gets the offset of the
+        smallest drawable weight (``q = 1``), so every entry is finite by construction.  One
+        tensor per ``num_neg``, kept: the loss checks and casts a table once per tensor object,
+        so asking again every step costs nothing."""
+        k = _num_neg_value(num_neg)
+        cache = self.__dict__.setdefault("_log_q", {})
+        t = cache.get(k)
+        if t is None:
+            t = cache[k] = torch.log(self.q.clamp(min=1).double() * float(k)
+                                     / float(self.T)).to(torch.float32)
+        return t
 
     def _table_args(self):
         """cdf, n_posts, T, guide, shift, n_guide in ABI order."""
