@@ -859,6 +859,34 @@ int hgnn_link_group(const int32_t* pu, const int32_t* pp, const int32_t* pn, int
                     int32_t* p_perm, int32_t* n_rowptr, int32_t* n_users_sorted, void* ws,
                     size_t ws_bytes, hgnn_stream_t stream);
 
+/* hgnn_link_group for n_neg >= 1 negatives per pair (pn[E * n_neg], row-major: row i the negatives
+ * of batch pair i) and two optional inputs (opt-in; minibatch.LinkLoss with num_neg / weighting=
+ * "edge" / logq).  The stable sort by user carries the batch position as its payload, and one
+ * kernel fills from it:
+ *   rowptr_u, col_p, uop, p_rowptr, p_users, p_perm   as hgnn_link_group
+ *   neg[E * n_neg]          row p = the negatives of user-grouped position p
+ *                           (hgnn_edge_score_fwd_k's layout)
+ *   n_rowptr[n_posts + 1] / n_users_sorted[E * n_neg]
+ *                           all E * n_neg (negative post, user) pairs grouped by post, stable
+ *   w != NULL (fp32 [E], batch order): w_user[E] = the weights by user-grouped position, w_post[E]
+ *                           = by post-grouped position, w_post[i] = w_user[p_perm[i]] (exact copies)
+ *   logq != NULL (fp32, the global table) with seeds_p[n_seeds] (the batch's local -> global post
+ *   ids): logq_local[n_posts], logq_local[j] = logq[seeds_p[j]] for j < the seeds' count — n_seeds,
+ *   or min(n_seeds, *d_n_seeds) when d_n_seeds (device int32, hgnn_link_seeds*'s d_counts + 1) is
+ *   given: the count then never leaves the device — and 0 for the rows after it (padded tables),
+ *   which no pair refers to.  logq and seeds_p are both given or both NULL.
+ * Nothing is read back; every launch is sized by E, n_neg, n_users, n_posts.  With n_neg = 1 and
+ * no optional input the nine common outputs equal hgnn_link_group's bit for bit.
+ * ws: hgnn_link_group_k_ws_bytes(E, n_neg). */
+size_t hgnn_link_group_k_ws_bytes(int64_t E, int32_t n_neg);
+int hgnn_link_group_k(const int32_t* pu, const int32_t* pp, const int32_t* pn, const float* w,
+                      const float* logq, const int32_t* seeds_p, int64_t n_seeds,
+                      const int32_t* d_n_seeds, int64_t E, int32_t n_neg, int64_t n_users,
+                      int64_t n_posts, int32_t* rowptr_u, int32_t* col_p, int32_t* neg,
+                      int32_t* uop, int32_t* p_rowptr, int32_t* p_users, int32_t* p_perm,
+                      int32_t* n_rowptr, int32_t* n_users_sorted, float* w_user, float* w_post,
+                      float* logq_local, void* ws, size_t ws_bytes, hgnn_stream_t stream);
+
 /* ---- sync-free static sampling (minibatch.StaticSampler; csrc/sampler_static.hip) ------------
  * The eager sampler's results (hgnn_sample_hop_count / _fill, hgnn_relabel_multi) followed by
  * hgnn_pad_csr_multi, written straight into static-capacity buffers with every count kept on
@@ -873,6 +901,19 @@ int hgnn_link_seeds(const int64_t* src, const int64_t* dst, const int64_t* edge_
                     const int64_t* neg, int64_t B, int32_t* seeds_u, int32_t* seeds_p,
                     int32_t* pu, int32_t* pp, int32_t* pn, int32_t* d_counts,
                     hgnn_stream_t stream);
+/* hgnn_link_seeds for n_neg >= 1 negatives per positive (opt-in; minibatch.LinkSampler with
+ * num_neg >= 2 or weighted draws): the negatives row-major [B, n_neg] as int64 (neg_i64,
+ * torch.randint's) or int32 (neg_i32, hgnn_weighted*_i32's) — exactly one of the two non-NULL.
+ * Block 1 ranks B * (1 + n_neg) post keys, the positives' posts first, then the negatives in
+ * row-major order: seeds_p[B * (1 + n_neg)] ascending and distinct, pp[B], pn[B * n_neg] the local
+ * ids in the same layout, d_counts[2].  Nothing past the counts is written.  Capacity:
+ * B * (1 + n_neg) <= 16384 keys (128 KiB of LDS in one workgroup; B = 1024 with n_neg <= 15,
+ * B = 2048 with n_neg <= 7), else HGNN_E_ARG before any launch.  With n_neg = 1 the outputs equal
+ * hgnn_link_seeds's. */
+int hgnn_link_seeds_k(const int64_t* src, const int64_t* dst, const int64_t* edge_ids,
+                      const int64_t* neg_i64, const int32_t* neg_i32, int64_t B, int32_t n_neg,
+                      int32_t* seeds_u, int32_t* seeds_p, int32_t* pu, int32_t* pp, int32_t* pn,
+                      int32_t* d_counts, hgnn_stream_t stream);
 
 /* One hop of n_rel (<= 8) relations, fanout 1..64: relation r samples the first *d_n_dst[r] ids
  * of dst_ids[r] (global CSR rowptrs[r] / cols[r] over n_rows[r] destinations; the count lives on

@@ -124,6 +124,12 @@ _SIGS = {
     "hgnn_link_group_ws_bytes": (_c_sz, [_c_i64]),
     "hgnn_link_group": (_c_i32, [_p, _p, _p, _c_i64, _c_i64, _c_i64, _p, _p, _p, _p, _p, _p, _p,
                                  _p, _p, _p, _c_sz, _p]),
+    "hgnn_link_seeds_k": (_c_i32, [_p, _p, _p, _p, _p, _c_i64, _c_i32, _p, _p, _p, _p, _p, _p,
+                                   _p]),
+    "hgnn_link_group_k_ws_bytes": (_c_sz, [_c_i64, _c_i32]),
+    "hgnn_link_group_k": (_c_i32, [_p, _p, _p, _p, _p, _p, _c_i64, _p, _c_i64, _c_i32, _c_i64,
+                                   _c_i64, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                                   _c_sz, _p]),
     "hgnn_relabel_multi": (_c_i32, [_c_i32, _p, _p, _p, _p, _p, _p, _p, _p, _c_i32, _p, _c_sz,
                                     _p]),
     "hgnn_topk_metrics": (_c_i32, [_p, _c_i64, _c_i64, _c_i64, _p, _p, _p, _c_i32, _p, _p, _p,

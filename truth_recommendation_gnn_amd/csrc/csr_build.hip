@@ -754,6 +754,116 @@ int hgnn_link_group(const int32_t* pu, const int32_t* pp, const int32_t* pn, int
 }  // extern "C"
 
 namespace hgnn {
+// User-grouped position i holds batch position b = perm[i] (the stable sort's payload): its post,
+// its n_neg negatives (row i of neg, the layout hgnn_edge_score_fwd_k reads), its weight, and its
+// user — the sorted key itself — once per position (uop) and once per negative (uop_k, the
+// payload of the negatives' sort; n_neg = 1: uop_k is uop).
+__global__ void k_link_fill_k(const int32_t* perm, const int32_t* users_sorted, const int32_t* pp,
+                              const int32_t* pn, const float* w, int64_t E, int32_t n_neg,
+                              int32_t* col_p, int32_t* neg, int32_t* uop, int32_t* uop_k,
+                              float* w_user) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= E) return;
+  const int64_t b = perm[i];
+  const int32_t u = users_sorted[i];
+  col_p[i] = pp[b];
+  uop[i] = u;
+  if (w) w_user[i] = w[b];
+  for (int j = 0; j < n_neg; ++j) {
+    neg[i * n_neg + j] = pn[b * n_neg + j];
+    if (uop_k != uop) uop_k[i * n_neg + j] = u;
+  }
+}
+
+// w_post[i] = w_user[p_perm[i]] for i < E; logq_local[j] = logq[seeds_p[j]] for j < the seeds'
+// count (n_seeds, or *d_n_seeds when the count lives on the device), 0 for the rows after it
+__global__ void k_link_finish_k(const float* w_user, const int32_t* p_perm, int64_t E,
+                                float* w_post, const float* logq, const int32_t* seeds_p,
+                                int64_t n_seeds, const int32_t* d_n_seeds, int64_t n_posts,
+                                float* logq_local) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (w_post && i < E) w_post[i] = w_user[p_perm[i]];
+  if (logq_local && i < n_posts) {
+    int64_t n = n_seeds;
+    if (d_n_seeds) n = min<int64_t>(n, *d_n_seeds);
+    logq_local[i] = i < n ? logq[seeds_p[i]] : 0.f;
+  }
+}
+}  // namespace hgnn
+
+extern "C" {
+
+size_t hgnn_link_group_k_ws_bytes(int64_t E, int32_t n_neg) {
+  const int64_t e = E < 1 ? 1 : E, k = n_neg < 1 ? 1 : n_neg;
+  return align_up((size_t)e * 4, 256) + align_up((size_t)(e * k) * 4, 256) +
+         sort_ws_bytes(e * k) + 256;
+}
+
+int hgnn_link_group_k(const int32_t* pu, const int32_t* pp, const int32_t* pn, const float* w,
+                      const float* logq, const int32_t* seeds_p, int64_t n_seeds,
+                      const int32_t* d_n_seeds, int64_t E, int32_t n_neg, int64_t n_users,
+                      int64_t n_posts, int32_t* rowptr_u, int32_t* col_p, int32_t* neg,
+                      int32_t* uop, int32_t* p_rowptr, int32_t* p_users, int32_t* p_perm,
+                      int32_t* n_rowptr, int32_t* n_users_sorted, float* w_user, float* w_post,
+                      float* logq_local, void* ws, size_t ws_bytes, hgnn_stream_t stream_) {
+  hipStream_t stream = as_stream(stream_);
+  if (E < 0 || n_neg < 1 || n_users < 1 || n_posts < 1 || n_users >= (int64_t(1) << 31) - 1 ||
+      n_posts >= (int64_t(1) << 31) - 1 || E * (int64_t)n_neg >= (int64_t(1) << 31) - 1)
+    return fail(HGNN_E_ARG, "link_group_k: E=%lld n_neg=%d n_users=%lld n_posts=%lld",
+                (long long)E, n_neg, (long long)n_users, (long long)n_posts);
+  if (!rowptr_u || !uop || !p_rowptr || !n_rowptr ||
+      (E > 0 && (!pu || !pp || !pn || !col_p || !neg || !p_users || !p_perm || !n_users_sorted)))
+    return fail(HGNN_E_ARG, "link_group_k: null pointer");
+  if (w && (!w_user || !w_post)) return fail(HGNN_E_ARG, "link_group_k: w without w_user / w_post");
+  if ((logq != nullptr) != (seeds_p != nullptr) || (logq && (!logq_local || n_seeds < 0)))
+    return fail(HGNN_E_ARG, "link_group_k: logq, seeds_p and logq_local go together");
+  if (ws_bytes < hgnn_link_group_k_ws_bytes(E, n_neg))
+    return fail(HGNN_E_WS, "link_group_k: workspace too small");
+  const int64_t Ek = E * n_neg;
+  Workspace own(ws, ws_bytes);
+  int32_t* perm = own.take<int32_t>(E < 1 ? 1 : E);
+  int32_t* uop_k = n_neg == 1 ? uop : own.take<int32_t>(Ek < 1 ? 1 : Ek);
+  const size_t off = align_up(own.used, 256);
+  char* sub = static_cast<char*>(ws) + off;   // the sorts' workspace, reused by each in turn
+  const size_t sub_bytes = ws_bytes - off;
+  if (E > 0) {
+    // the batch positions by user (stable), then everything that follows a pair from them
+    Workspace sw(sub, sub_bytes);
+    int32_t* ka = sw.take<int32_t>(E);
+    const int32_t* sk = nullptr;
+    if (int rc = radix_sort_pairs(pu, ka, E, n_users, nullptr, nullptr, perm, nullptr, sw, stream,
+                                  &sk))
+      return rc;
+    hipLaunchKernelGGL(k_rowptr_from_sorted, dim3(cdiv(n_users + 1, 256)), dim3(256), 0, stream,
+                       sk, E, n_users, rowptr_u);
+    if (int rc = check_launch("k_rowptr_from_sorted")) return rc;
+    hipLaunchKernelGGL(k_link_fill_k, dim3(cdiv(E, 256)), dim3(256), 0, stream, perm, sk, pp, pn,
+                       w, E, n_neg, col_p, neg, uop, uop_k, w_user);
+    if (int rc = check_launch("k_link_fill_k")) return rc;
+  } else {
+    hipLaunchKernelGGL(k_fill_i32, dim3(cdiv(n_users + 1, 256)), dim3(256), 0, stream, rowptr_u,
+                       n_users + 1, 0);
+  }
+  // the same pairs by post, and the E * n_neg (negative post, user) pairs by post
+  if (int rc = hgnn_csr_transpose(rowptr_u, col_p, n_users, E, n_posts, p_rowptr, p_users, p_perm,
+                                  nullptr, sub, sub_bytes, stream_))
+    return rc;
+  if (int rc = hgnn_sort_pairs_i32(neg, uop_k, nullptr, Ek, n_posts, n_rowptr, n_users_sorted,
+                                   nullptr, nullptr, sub, sub_bytes, stream_))
+    return rc;
+  const int64_t span = std::max<int64_t>(w && E > 0 ? E : 0, logq ? n_posts : 0);
+  if (span > 0) {
+    hipLaunchKernelGGL(k_link_finish_k, dim3(cdiv(span, 256)), dim3(256), 0, stream, w_user,
+                       p_perm, E, (w && E > 0) ? w_post : nullptr, logq, seeds_p, n_seeds,
+                       d_n_seeds, n_posts, logq ? logq_local : nullptr);
+    return check_launch("k_link_finish_k");
+  }
+  return HGNN_OK;
+}
+
+}  // extern "C"
+
+namespace hgnn {
 // The CSCs of several destination-grouped CSRs in one sort: relation r's columns are keyed
 // col + cbase[r] and its positions numbered from ebase[r], so one stable sort over the combined
 // key range groups every relation's entries by (relation, column); each output then takes its

@@ -10,6 +10,8 @@
 //                          pair's local ids (torch.unique + searchsorted of minibatch.link_batch):
 //                          one workgroup per node type sorts its keys in LDS (bitonic), ranks the
 //                          distinct ones with one block scan and scatters the ranks back
+//   hgnn_link_seeds_k      the same for k >= 1 negatives per positive, int64 or int32 draws: up to
+//                          16384 post keys in one workgroup's LDS
 //   hgnn_sample_hop_static one hop (count, scan, rowptr + padding, fill) over the frontier's
 //                          capacity, each relation's real destination count read on the device
 //   hgnn_relabel_static    the next frontier (hgnn_relabel_multi's order: prefix first, then new
@@ -101,6 +103,99 @@ __global__ void __launch_bounds__(1024) k_link_seeds(const int64_t* src, const i
       if (f[q]) seeds_p[u] = skey[j];
       if (idx < B) pp[idx] = u;
       else pn[idx - B] = u;
+    }
+  }
+  if (tid == 1023) {
+    int tot = 0;
+    for (int w = 0; w < 16; ++w) tot += wsum[w];
+    d_counts[b] = tot;
+  }
+}
+
+// k_link_seeds for n_neg >= 1 negatives per positive (row-major [B, n_neg], int64 or int32):
+// block 1 ranks B * (1 + n_neg) post keys, the positives' posts first.  CAP = the keys one block
+// holds: 4096 as above, or 16384 — 128 KiB of (key, index) pairs, which one workgroup may declare
+// on gfx950 (160 KiB per CU); a thread's rank scan then covers up to CAP / 1024 entries.
+constexpr int kSeedMaxK = 16384;
+
+template <int CAP>
+__global__ void __launch_bounds__(1024) k_link_seeds_k(
+    const int64_t* src, const int64_t* dst, const int64_t* eid, const int64_t* neg64,
+    const int32_t* neg32, int64_t B, int32_t n_neg, int32_t* seeds_u, int32_t* seeds_p,
+    int32_t* pu, int32_t* pp, int32_t* pn, int32_t* d_counts) {
+  constexpr int kPer = CAP / 1024;
+  __shared__ int32_t skey[CAP], sidx[CAP];
+  __shared__ int32_t wsum[16];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int nB = (int)B;
+  const int n = b == 0 ? nB : nB * (1 + n_neg);   // <= CAP (checked by the caller)
+  int P = 1;
+  while (P < n) P <<= 1;
+  for (int i = tid; i < P; i += 1024) {
+    int32_t k = INT32_MAX;
+    if (i < n) {
+      if (b == 0) k = (int32_t)src[eid[i]];
+      else if (i < nB) k = (int32_t)dst[eid[i]];
+      else k = neg64 ? (int32_t)neg64[i - nB] : neg32[i - nB];
+    }
+    skey[i] = k;
+    sidx[i] = i < n ? i : INT32_MAX;
+  }
+  __syncthreads();
+  // bitonic sort of (key, index) ascending
+  for (int size = 2; size <= P; size <<= 1) {
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = tid; i < P; i += 1024) {
+        const int j = i ^ stride;
+        if (j > i) {
+          const bool up = (i & size) == 0;
+          const int32_t ki = skey[i], kj = skey[j], ii = sidx[i], ij = sidx[j];
+          if (seed_less(kj, ij, ki, ii) == up) {
+            skey[i] = kj; skey[j] = ki;
+            sidx[i] = ij; sidx[j] = ii;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  // rank of the distinct keys: each thread scans PER = P / 1024 (<= kPer) consecutive entries
+  const int PER = P >= 1024 ? P / 1024 : 1;
+  const int j0 = tid * PER;
+  uint32_t f = 0;   // bit q: entry j0 + q starts a new key
+  int s = 0;
+  for (int q = 0; q < kPer; ++q) {
+    const int j = j0 + q;
+    if (q < PER && j < n && (j == 0 || skey[j] != skey[j - 1])) {
+      f |= 1u << q;
+      ++s;
+    }
+  }
+  const int lane = tid & 63, wv = tid >> 6;
+  int x = s;
+  for (int o = 1; o < 64; o <<= 1) {
+    const int y = __shfl_up(x, o, 64);
+    if (lane >= o) x += y;
+  }
+  if (lane == 63) wsum[wv] = x;
+  __syncthreads();
+  int before = 0;
+  for (int w = 0; w < wv; ++w) before += wsum[w];
+  int r = before + x - s;   // distinct keys before this thread's first entry
+  for (int q = 0; q < PER; ++q) {
+    const int j = j0 + q;
+    if (j >= n) break;
+    const bool first = (f >> q) & 1u;
+    r += first ? 1 : 0;
+    const int u = r - 1;   // the rank of entry j's key
+    const int32_t idx = sidx[j];
+    if (b == 0) {
+      if (first) seeds_u[u] = skey[j];
+      pu[idx] = u;
+    } else {
+      if (first) seeds_p[u] = skey[j];
+      if (idx < nB) pp[idx] = u;
+      else pn[idx - nB] = u;
     }
   }
   if (tid == 1023) {
@@ -285,6 +380,28 @@ int hgnn_link_seeds(const int64_t* src, const int64_t* dst, const int64_t* edge_
   hipLaunchKernelGGL(k_link_seeds, dim3(2), dim3(1024), 0, as_stream(stream), src, dst, edge_ids,
                      neg, B, seeds_u, seeds_p, pu, pp, pn, d_counts);
   return check_launch("k_link_seeds");
+}
+
+int hgnn_link_seeds_k(const int64_t* src, const int64_t* dst, const int64_t* edge_ids,
+                      const int64_t* neg_i64, const int32_t* neg_i32, int64_t B, int32_t n_neg,
+                      int32_t* seeds_u, int32_t* seeds_p, int32_t* pu, int32_t* pp, int32_t* pn,
+                      int32_t* d_counts, hgnn_stream_t stream) {
+  if (B < 1 || n_neg < 1 || B > kSeedMaxK || B * (1 + (int64_t)n_neg) > kSeedMaxK)
+    return fail(HGNN_E_ARG, "link_seeds_k: B=%lld positives x (1 + %d negatives): 1..%d post keys",
+                (long long)B, n_neg, kSeedMaxK);
+  if ((neg_i64 == nullptr) == (neg_i32 == nullptr))
+    return fail(HGNN_E_ARG, "link_seeds_k: exactly one of neg_i64 / neg_i32");
+  if (!src || !dst || !edge_ids || !seeds_u || !seeds_p || !pu || !pp || !pn || !d_counts)
+    return fail(HGNN_E_ARG, "link_seeds_k: null pointer");
+  if (B * (1 + (int64_t)n_neg) <= kSeedMax)
+    hipLaunchKernelGGL(k_link_seeds_k<kSeedMax>, dim3(2), dim3(1024), 0, as_stream(stream), src,
+                       dst, edge_ids, neg_i64, neg_i32, B, n_neg, seeds_u, seeds_p, pu, pp, pn,
+                       d_counts);
+  else
+    hipLaunchKernelGGL(k_link_seeds_k<kSeedMaxK>, dim3(2), dim3(1024), 0, as_stream(stream), src,
+                       dst, edge_ids, neg_i64, neg_i32, B, n_neg, seeds_u, seeds_p, pu, pp, pn,
+                       d_counts);
+  return check_launch("k_link_seeds_k");
 }
 
 int hgnn_sample_hop_static(int32_t n_rel, const int32_t* const* rowptrs,

@@ -581,14 +581,54 @@ class LinkLoss:
     copy); ``load`` = both.  ``n_total`` = the positives of ALL ranks, so per-rank
     losses add up to the global batch's mean (data-parallel gradients are summed).  It reads the
     seed rows by local id, so a batch with fewer distinct endpoints than the capacity is fine
-    (``partial_seeds``)."""
+    (``partial_seeds``).
+
+    Opt-in, each the full-graph loss's option of the same name (``ops.edge_bce_loss``) on the
+    batch's pairs; with none of them this is the class it was, the same calls into the same
+    arena layout:
+
+    * ``num_neg`` = k >= 2: k negatives per positive, ``pn`` of shape ``[E, k]``; ``n_posts`` is
+      then the post-seed capacity ``(1 + k) * n_edges`` of a ``LinkSampler``;
+    * ``weighting="edge"``: ``prepare`` takes ``w`` (fp32 ``[E]``, the pairs' weights in batch
+      order), staged in the two kernel orders (an ``ops.EdgeWeights`` over the live views); the
+      kernels get ``cscale`` = 1;
+    * ``logq``: the GLOBAL ``[num_posts]`` table (e.g. ``PostDistribution.log_q(k)``), checked
+      here once (shape, dtype, finite: the one host sync) and kept as contiguous fp32;
+      ``prepare`` takes ``seeds_p`` (the batch's local -> global post ids) and stages
+      ``logq[seeds_p]``, the table the kernels read by local id.
+
+    Anything but the default is staged by ``hgnn_link_group_k`` (one stable sort by user that
+    carries the batch position, one fill kernel, the two groupings by post).  ``n_total`` keeps
+    its meaning: the positives weigh ``1 / n_total`` each (times ``w``), the negatives
+    ``1 / (n_total * k)``.  The negatives keep the unplanned dP gather whatever they were drawn
+    from."""
 
     partial_seeds = True
+    _NINE = ("rowptr", "col", "neg", "uop", "p_rowptr", "p_users", "p_perm", "n_rowptr",
+             "n_users")
 
-    def __init__(self, n_edges: int, n_users: int, n_posts: int, device, n_total: int = 0):
+    def __init__(self, n_edges: int, n_users: int, n_posts: int, device, n_total: int = 0, *,
+                 num_neg: int = 1, weighting: str = "mean",
+                 logq: Optional[torch.Tensor] = None):
         self.E, self.n_users, self.n_posts = int(n_edges), int(n_users), int(n_posts)
         self.n_total = int(n_total) if n_total else self.E
         self.device = torch.device(device)
+        self.num_neg = ops._num_neg_value(num_neg)
+        self.weighting = ops._weighting_value(weighting, "LinkLoss")
+        self.per_edge = self.weighting == "edge"
+        self.logq = None
+        if logq is not None:
+            if isinstance(logq, torch.Tensor) and logq.dim() != 1:
+                raise ValueError(f"LinkLoss: logq of shape {list(logq.shape)}; expected "
+                                 "[num_posts], one entry per post of the graph")
+            ops._logq_rules(logq, int(logq.shape[0]) if isinstance(logq, torch.Tensor) else 0,
+                            "LinkLoss")
+            t = logq.detach().to(device=self.device, dtype=torch.float32).contiguous()
+            if not bool(torch.isfinite(t).all()):
+                raise ValueError("LinkLoss: logq must be finite (PostDistribution.log_q gives a "
+                                 "post of weight 0 the smallest drawable weight's entry)")
+            self.logq = t
+        self._default = self.num_neg == 1 and not self.per_edge and self.logq is None
         self.cscale = torch.ones((), dtype=torch.float32, device=self.device)
         self._alloc(self.n_users, self.n_posts)
 
@@ -603,27 +643,38 @@ class LinkLoss:
     def use_direct(self) -> None:
         """Prepare straight into the live buffers (see ``StaticBlocks.use_direct``)."""
         self.arena.direct = True
+        self._set_stage_ptrs()
+
+    def _set_stage_ptrs(self) -> None:
         st = self.arena.target()
-        self._stage_ptrs = tuple(st[k].data_ptr() for k in (
-            "rowptr", "col", "neg", "uop", "p_rowptr", "p_users", "p_perm", "n_rowptr",
-            "n_users"))
+        self._stage_ptrs = tuple(st[k].data_ptr() for k in self._NINE)
+        # hgnn_link_group_k's optional outputs: w_user, w_post, logq_local
+        self._opt_ptrs = tuple(st[k].data_ptr() if k in st else None
+                               for k in ("w_user", "w_post", "logq"))
 
     def _alloc(self, rows_u: int, rows_p: int) -> None:
-        i32, E = torch.int32, self.E
+        i32, f32, E, k = torch.int32, torch.float32, self.E, self.num_neg
         self.rows = {"user": rows_u, "post": rows_p}
-        self.arena = _Arena({"rowptr": (rows_u + 1, i32), "col": (E, i32),
-                             "neg": (E, i32), "uop": (E, i32),
-                             "p_rowptr": (rows_p + 1, i32), "p_users": (E, i32),
-                             "p_perm": (E, i32), "n_rowptr": (rows_p + 1, i32),
-                             "n_users": (E, i32)}, self.device)
+        spec = {"rowptr": (rows_u + 1, i32), "col": (E, i32),
+                "neg": (E * k, i32), "uop": (E, i32),
+                "p_rowptr": (rows_p + 1, i32), "p_users": (E, i32),
+                "p_perm": (E, i32), "n_rowptr": (rows_p + 1, i32),
+                "n_users": (E * k, i32)}
+        # (the optional entries go last and only when asked for: the default layout is unchanged)
+        if self.per_edge:
+            spec["w_user"] = (E, f32)
+            spec["w_post"] = (E, f32)
+        if self.logq is not None:
+            spec["logq"] = (rows_p, f32)
+        self.arena = _Arena(spec, self.device)
         self.csr: Optional[_LossCSR] = None
         self.presorted = None
-        st = self.arena.stage
-        self._stage_ptrs = tuple(st[k].data_ptr() for k in (
-            "rowptr", "col", "neg", "uop", "p_rowptr", "p_users", "p_perm", "n_rowptr",
-            "n_users"))
-        self._ws = torch.empty(max(int(N.lib().hgnn_link_group_ws_bytes(self.E)), 256),
-                               dtype=torch.uint8, device=self.device)
+        self.edge_w = None
+        self._set_stage_ptrs()
+        lib = N.lib()
+        ws = (lib.hgnn_link_group_ws_bytes(self.E) if self._default
+              else lib.hgnn_link_group_k_ws_bytes(self.E, k))
+        self._ws = torch.empty(max(int(ws), 256), dtype=torch.uint8, device=self.device)
 
     # the live buffers under their round-5 names
     rowptr = property(lambda self: self.arena.live["rowptr"])
@@ -631,29 +682,85 @@ class LinkLoss:
     neg = property(lambda self: self.arena.live["neg"])
     uop = property(lambda self: self.arena.live["uop"])
 
-    def prepare(self, pu: torch.Tensor, pp: torch.Tensor, pn: torch.Tensor) -> None:
-        if int(pu.numel()) != self.E:
-            raise ValueError(f"{int(pu.numel())} positives for a {self.E}-edge link loss")
+    def prepare(self, pu: torch.Tensor, pp: torch.Tensor, pn: torch.Tensor,
+                w: Optional[torch.Tensor] = None, seeds_p: Optional[torch.Tensor] = None, *,
+                seeds_count: Optional[torch.Tensor] = None) -> None:
+        """``pn``: ``[E]`` or ``[E, k]`` with k = ``num_neg``; ``w`` (``[E]``, batch order):
+        exactly with ``weighting="edge"``; ``seeds_p`` (the batch's post seeds, local -> global):
+        exactly with ``logq``.  ``seeds_count`` (device int32, one element): the number of valid
+        entries of a fixed-capacity ``seeds_p`` (``LinkSampler``'s, whose count never leaves the
+        device); without it all of ``seeds_p`` is valid.  Table rows past the seeds get 0."""
+        if self._default and w is None and seeds_p is None and pn.dim() == 1:
+            # the reference's loss: the call it always was (the cfg5 loop is bound by the host,
+            # so this path takes no further checks)
+            if int(pu.numel()) != self.E:
+                raise ValueError(f"{int(pu.numel())} positives for a {self.E}-edge link loss")
+            pu, pp, pn = (t.to(torch.int32).contiguous() for t in (pu, pp, pn))
+            self.arena.wait_committed()
+            N.check(N.lib().hgnn_link_group(
+                N.ptr(pu), N.ptr(pp), N.ptr(pn), self.E, self.rows["user"], self.rows["post"],
+                *self._stage_ptrs, self._ws.data_ptr(), self._ws.numel(),
+                N.stream_ptr(self.device)), "hgnn_link_group")
+            return
+        E, k = self.E, self.num_neg
+        if int(pu.numel()) != E:
+            raise ValueError(f"{int(pu.numel())} positives for a {E}-edge link loss")
+        shape = tuple(pn.shape)
+        if shape not in (((E,), (E, 1)) if k == 1 else ((E, k),)):
+            raise ValueError(f"LinkLoss.prepare: pn of shape {list(shape)}; expected "
+                             f"[{E}{'' if k == 1 else f', {k}'}] (num_neg={k})")
+        if (w is not None) != self.per_edge:
+            raise ValueError("LinkLoss.prepare: w " + (
+                f"(the pairs' weights, [{E}]) is required with weighting='edge'" if self.per_edge
+                else "is taken only by a LinkLoss made with weighting='edge'"))
+        if w is not None and tuple(w.shape) != (E,):
+            raise ValueError(f"LinkLoss.prepare: w of shape {list(w.shape)}; expected [{E}]")
+        if (seeds_p is not None) != (self.logq is not None):
+            raise ValueError("LinkLoss.prepare: seeds_p " + (
+                "(the batch's post seeds) is required with logq" if self.logq is not None
+                else "is taken only by a LinkLoss made with logq"))
+        if seeds_p is not None and (seeds_p.dim() != 1
+                                    or int(seeds_p.numel()) > self.rows["post"]):
+            raise ValueError(f"LinkLoss.prepare: seeds_p of shape {list(seeds_p.shape)}; at most "
+                             f"{self.rows['post']} post seeds")
         pu, pp, pn = (t.to(torch.int32).contiguous() for t in (pu, pp, pn))
+        if self._default:
+            self.arena.wait_committed()
+            N.check(N.lib().hgnn_link_group(
+                N.ptr(pu), N.ptr(pp), N.ptr(pn), E, self.rows["user"], self.rows["post"],
+                *self._stage_ptrs, self._ws.data_ptr(), self._ws.numel(),
+                N.stream_ptr(self.device)), "hgnn_link_group")
+            return
+        if w is not None:
+            w = w.detach().to(torch.float32).contiguous()
+        if seeds_p is not None:
+            seeds_p = seeds_p.to(torch.int32).contiguous()
         self.arena.wait_committed()
-        N.check(N.lib().hgnn_link_group(
-            N.ptr(pu), N.ptr(pp), N.ptr(pn), self.E, self.rows["user"], self.rows["post"],
-            *self._stage_ptrs, self._ws.data_ptr(), self._ws.numel(),
-            N.stream_ptr(self.device)), "hgnn_link_group")
+        N.check(N.lib().hgnn_link_group_k(
+            N.ptr(pu), N.ptr(pp), N.ptr(pn), N.ptr(w), N.ptr(self.logq), N.ptr(seeds_p),
+            int(seeds_p.numel()) if seeds_p is not None else 0, N.ptr(seeds_count), E, k,
+            self.rows["user"], self.rows["post"], *self._stage_ptrs, *self._opt_ptrs,
+            self._ws.data_ptr(), self._ws.numel(), N.stream_ptr(self.device)),
+            "hgnn_link_group_k")
 
     def commit(self) -> None:
         self.arena.commit()
 
-    def load(self, pu: torch.Tensor, pp: torch.Tensor, pn: torch.Tensor) -> None:
-        self.prepare(pu, pp, pn)
+    def load(self, pu: torch.Tensor, pp: torch.Tensor, pn: torch.Tensor,
+             w: Optional[torch.Tensor] = None, seeds_p: Optional[torch.Tensor] = None) -> None:
+        self.prepare(pu, pp, pn, w, seeds_p)
         self.commit()
 
     def make_csr(self) -> None:
         lv = self.arena.live
         nu, np_ = self.rows["user"], self.rows["post"]
         self.csr = _LossCSR(lv, nu, np_)
-        self.presorted = ops.PresortedNegatives(self.csr, lv["neg"], "user", np_,
-                                                lv["n_rowptr"], lv["n_users"])
+        k = self.num_neg
+        self._neg = lv["neg"] if k == 1 else lv["neg"].view(self.E, k)
+        self.presorted = ops.PresortedNegatives(self.csr, self._neg, "user", np_,
+                                                lv["n_rowptr"], lv["n_users"], k=k)
+        self.edge_w = (ops.EdgeWeights(lv["w_user"], lv["w_post"], self.cscale)
+                       if self.per_edge else None)
 
     def __call__(self, out: Mapping[str, torch.Tensor]) -> torch.Tensor:
         U, P = out["user"], out["post"]
@@ -663,9 +770,16 @@ class LinkLoss:
                              f"{tuple(U.shape)} / {tuple(P.shape)}")
         if self.csr is None:
             self.make_csr()
-        return ops._EdgeBCELoss.apply(U, P, self.csr, self.arena.live["neg"], self.cscale,
-                                      False, self.n_total, None,
-                                      self.presorted if self.E else None)
+        if self._default:
+            return ops._EdgeBCELoss.apply(U, P, self.csr, self.arena.live["neg"], self.cscale,
+                                          False, self.n_total, None,
+                                          self.presorted if self.E else None)
+        # (weighting="edge": cscale is the constant 1; the local logQ table is the live view,
+        # rewritten per batch — ops.logq_table's per-tensor check would be a host sync here)
+        return ops._EdgeBCELoss.apply(U, P, self.csr, self._neg, self.cscale, False,
+                                      self.n_total, None, self.presorted if self.E else None,
+                                      False, self.edge_w,
+                                      self.arena.live["logq"] if self.logq is not None else None)
 
 
 @dataclasses.dataclass
@@ -673,7 +787,9 @@ class LinkBatch:
     """A link-prediction mini-batch (PyG LinkNeighborLoader semantics, binary negatives): B
     positive ``engages`` edges, one uniform negative post per positive (train_gnn.py:272), the
     seeds = the distinct endpoints (users; posts of the positives and negatives, each sorted),
-    and the pairs as local ids into the seeds (= the sampled outputs' rows)."""
+    and the pairs as local ids into the seeds (= the sampled outputs' rows).  With ``num_neg`` =
+    k >= 2 negatives per positive ``neg_p`` / ``pn`` are ``[B, k]``; ``w``: the positives'
+    weights (fp32 ``[B]``, batch order) when ``link_batch`` was given ``pos_weights``."""
     pos_u: torch.Tensor      # global ids [B]
     pos_p: torch.Tensor
     neg_p: torch.Tensor
@@ -682,21 +798,84 @@ class LinkBatch:
     pp: torch.Tensor
     pn: torch.Tensor
     mb: Optional[MiniBatch] = None
+    w: Optional[torch.Tensor] = None
+
+
+def _check_draw_args(who: str, num_posts: int, distribution, avoid, max_tries) -> None:
+    """``distribution`` / ``avoid`` / ``max_tries`` of a link batch's negatives, as
+    ``ops.sample_negatives`` checks them (before anything touches the device)."""
+    if distribution is not None and not isinstance(distribution, ops.PostDistribution):
+        raise ValueError(f"{who}: distribution must be a PostDistribution")
+    if int(max_tries) != max_tries or max_tries < 1:
+        raise ValueError(f"{who}: max_tries={max_tries!r}; at least 1 attempt")
+    if num_posts < 1 or num_posts >= 2**31:
+        raise ValueError(f"{who}: num_posts={num_posts} out of range")
+    if distribution is not None and distribution.num_posts != int(num_posts):
+        raise ValueError(f"{who}: the distribution is over {distribution.num_posts} posts, "
+                         f"num_posts={num_posts}")
+    if avoid is not None and int(getattr(avoid, "num_posts", -1)) != int(num_posts):
+        raise ValueError(f"{who}: avoid indexes {getattr(avoid, 'num_posts', None)} posts, "
+                         f"num_posts={num_posts}")
+
+
+def _draw_link_negatives(pos_u: torch.Tensor, num_posts: int, num_neg: int, generator,
+                         distribution, avoid, max_tries: int) -> torch.Tensor:
+    """A link batch's negatives, ``[B]`` or ``[B, num_neg]`` (no host sync).  Uniform: one
+    ``torch.randint`` in ``pos_u``'s dtype (the reference's draw, train_gnn.py:272).  With
+    ``distribution`` and / or ``avoid``: int32 draws as ``ops.sample_negatives`` makes them — one
+    device seed from ``generator``, draw i * num_neg + j being negative j of batch position i, a
+    draw that position's user ``pos_u[i]`` has seen drawn again up to ``max_tries`` attempts."""
+    B, dev = int(pos_u.numel()), pos_u.device
+    shape = (B,) if num_neg == 1 else (B, num_neg)
+    if distribution is None and avoid is None:
+        return torch.randint(0, int(num_posts), shape, device=dev, generator=generator,
+                             dtype=pos_u.dtype)
+    out = torch.empty(shape, dtype=torch.int32, device=dev)
+    if B == 0:
+        return out
+    lib, s = N.lib(), N.stream_ptr(dev)
+    seed = torch.randint(0, 2**62, (1,), device=dev, dtype=torch.int64, generator=generator)
+    table = (distribution._table_args() if distribution is not None
+             else (None, int(num_posts), 0, None, 0, 0))
+    n = B * num_neg
+    if avoid is None:
+        N.check(lib.hgnn_weighted_i32(N.ptr(seed), n, *table, N.ptr(out), s),
+                "hgnn_weighted_i32")
+        return out
+    users = pos_u.to(torch.int32).contiguous()
+    N.check(lib.hgnn_weighted_avoid_i32(
+        N.ptr(seed), n, num_neg, *table, N.ptr(users), avoid.num_users, N.ptr(avoid.rowptr),
+        N.ptr(avoid._col), int(max_tries), N.ptr(out), None, s), "hgnn_weighted_avoid_i32")
+    return out
 
 
 def link_batch(edge_index: torch.Tensor, edge_ids: torch.Tensor, num_posts: int,
-               generator: Optional[torch.Generator] = None) -> LinkBatch:
+               generator: Optional[torch.Generator] = None, num_neg: int = 1, *,
+               distribution=None, avoid=None, max_tries: int = 4,
+               pos_weights: Optional[torch.Tensor] = None) -> LinkBatch:
     """The positives ``edge_index[:, edge_ids]`` ((user, post) rows), their negatives drawn
     uniformly over the posts, the distinct endpoints as seeds (two host syncs: the unique
-    counts)."""
+    counts).
+
+    ``num_neg`` = k >= 2: ``torch.randint(0, num_posts, (B, k))``.  ``distribution`` (an
+    ``ops.PostDistribution``) and / or ``avoid`` (a ``metrics.SeenIndex``): int32 negatives drawn
+    by popularity and / or redrawn while the positive's user has seen them
+    (``_draw_link_negatives``).  ``pos_weights`` (one per edge of ``edge_index``): the batch's
+    ``w = pos_weights[edge_ids]`` as fp32.  The defaults are the function it was."""
+    num_neg = ops._num_neg_value(num_neg)
+    _check_draw_args("link_batch", int(num_posts), distribution, avoid, max_tries)
+    if pos_weights is not None and tuple(pos_weights.shape) != (int(edge_index.shape[1]),):
+        raise ValueError(f"link_batch: pos_weights of shape {list(pos_weights.shape)}; expected "
+                         f"[{int(edge_index.shape[1])}], one per edge of edge_index")
     pos_u, pos_p = edge_index[0, edge_ids], edge_index[1, edge_ids]
-    neg_p = torch.randint(0, int(num_posts), (int(edge_ids.numel()),), device=pos_u.device,
-                          generator=generator, dtype=pos_u.dtype)
+    neg_p = _draw_link_negatives(pos_u, int(num_posts), num_neg, generator, distribution, avoid,
+                                 max_tries)
     su = torch.unique(pos_u)
-    sp = torch.unique(torch.cat([pos_p, neg_p]))
+    sp = torch.unique(torch.cat([pos_p, neg_p.reshape(-1).to(pos_p.dtype)]))
+    w = None if pos_weights is None else pos_weights[edge_ids].to(torch.float32)
     return LinkBatch(pos_u, pos_p, neg_p, {"user": su, "post": sp},
                      torch.searchsorted(su, pos_u), torch.searchsorted(sp, pos_p),
-                     torch.searchsorted(sp, neg_p))
+                     torch.searchsorted(sp, neg_p.to(pos_p.dtype)), w=w)
 
 
 class LinkSampler:
@@ -709,29 +888,65 @@ class LinkSampler:
     bytes equal ``link_batch`` + ``NeighborSampler.sample`` + ``CapturedStep.prepare`` on the
     same edges, draws and seed (tested), so the replayed step is unchanged; the host only
     queues ~10 calls (the eager sampler's read-backs made the host loop the
-    cfg5 bound).  ``edge_ids``: the batch's positive edges into ``edge_index`` (int64 [B])."""
+    cfg5 bound).  ``edge_ids``: the batch's positive edges into ``edge_index`` (int64 [B]).
+
+    The loss's options are the sampler's: with a ``LinkLoss`` made for ``num_neg`` = k the
+    post-seed capacity must be ``(1 + k) * B`` and the batch's ``[B, k]`` negatives, seeds and
+    local ids come from ``hgnn_link_seeds_k`` (k >= 2 or int32 draws; ``B * (1 + k)`` <= 16384);
+    ``distribution`` / ``avoid`` / ``max_tries`` draw them as ``link_batch`` does with the same
+    arguments and generator; ``pos_weights`` (one per edge of ``edge_index``) is required
+    exactly when the loss has ``weighting="edge"`` and gives the batch's ``pos_weights[edge_ids]``;
+    with ``logq`` the loss stages ``logq[seeds]`` from this sampler's seed buffer and its
+    device-side count.  Still no host sync; without any of it, the calls it made before."""
 
     def __init__(self, step: CapturedStep, edge_index: torch.Tensor, num_posts: int,
-                 loss: Optional["LinkLoss"] = None):
+                 loss: Optional["LinkLoss"] = None, *, distribution=None, avoid=None,
+                 max_tries: int = 4, pos_weights: Optional[torch.Tensor] = None):
         blocks = step.blocks
         loss = step.loss_fn if loss is None else loss     # the LinkLoss the step's loss reads
         smp = blocks.smp
         if not isinstance(getattr(loss, "arena", None), _Arena) or not hasattr(loss, "n_users"):
             raise ValueError("LinkSampler stages a LinkLoss (its loss_fn)")
-        if set(blocks.n_seeds) != {"user", "post"} or blocks.n_seeds["post"] != 2 * loss.E \
-                or blocks.n_seeds["user"] != loss.E:
-            raise ValueError("LinkSampler: seeds capacities must be B users and 2B posts")
+        # the loss's options (num_neg, weighting, logq) are the sampler's
+        k = int(getattr(loss, "num_neg", 1))
+        per_edge = bool(getattr(loss, "per_edge", False))
+        logq = getattr(loss, "logq", None)
+        if set(blocks.n_seeds) != {"user", "post"} or \
+                blocks.n_seeds["post"] != (1 + k) * loss.E or blocks.n_seeds["user"] != loss.E:
+            raise ValueError("LinkSampler: seeds capacities must be B users and "
+                             + ("2B posts" if k == 1 else f"(1 + {k})B posts (num_neg={k})"))
         if blocks.L < 2:
             raise ValueError("LinkSampler: at least two layers (the outermost block's "
                              "destinations are an inner hop's relabelled frontier)")
+        _check_draw_args("LinkSampler", int(num_posts), distribution, avoid, max_tries)
+        if per_edge != (pos_weights is not None) or (
+                per_edge and tuple(pos_weights.shape) != (int(edge_index.shape[1]),)):
+            raise ValueError("LinkSampler: pos_weights " + (
+                f"of shape [{int(edge_index.shape[1])}], one per edge of edge_index, is required "
+                "by a LinkLoss with weighting='edge'" if per_edge
+                else "is taken only with a LinkLoss made with weighting='edge'"))
+        if logq is not None and int(logq.numel()) != int(num_posts):
+            raise ValueError(f"LinkSampler: the LinkLoss's logq has {int(logq.numel())} entries, "
+                             f"num_posts={int(num_posts)}")
+        self.num_neg, self.distribution, self.avoid = k, distribution, avoid
+        self.max_tries = int(max_tries)
+        # hgnn_link_seeds_k: k >= 2, or int32 (weighted / seen-avoiding) draws
+        self._seeds_k = k >= 2 or distribution is not None or avoid is not None
+        self._loss_default = bool(getattr(loss, "_default", True))
+        if self._seeds_k and (1 + k) * loss.E > 16384:
+            raise ValueError(f"LinkSampler: {loss.E} positives x (1 + {k}) post keys exceed "
+                             "hgnn_link_seeds_k's 16384 per batch")
+        self.pos_weights = (pos_weights.detach().to(torch.float32).contiguous() if per_edge
+                            else None)
         self.step, self.blocks, self.loss = step, blocks, loss
         self.edge_index, self.num_posts, self.B = edge_index, int(num_posts), loss.E
         dev, i32, L = smp.device, torch.int32, blocks.L
         lib = N.lib()
         B = self.B
         self.seeds = {"user": torch.zeros(B, dtype=i32, device=dev),
-                      "post": torch.zeros(2 * B, dtype=i32, device=dev)}
-        self.pairs = torch.zeros(3, B, dtype=i32, device=dev)          # pu, pp, pn
+                      "post": torch.zeros((1 + k) * B, dtype=i32, device=dev)}
+        self.pairs = torch.zeros(2 + k, B, dtype=i32, device=dev)      # pu, pp, pn ([B, k] flat)
+        self._pair_views = (self.pairs[0], self.pairs[1], self.pairs[2:].view(-1))
         self.zero = torch.zeros(2, dtype=i32, device=dev)
         # per level: node counts per type (level 0: the seed kernel's [users, posts])
         self.counts = [torch.zeros(max(len(blocks.cap[h]), 2), dtype=i32, device=dev)
@@ -808,17 +1023,33 @@ class LinkSampler:
             raise ValueError(f"{int(edge_ids.numel())} positives for a {self.B}-pair batch")
         dev = self.blocks.smp.device
         eid = edge_ids.to(torch.int64).contiguous()
+        ei, k = self.edge_index, self.num_neg
         # the negatives exactly as link_batch draws them (same generator, same call)
-        neg = torch.randint(0, self.num_posts, (self.B,), device=dev, generator=generator,
-                            dtype=self.edge_index.dtype)
+        if not self._seeds_k:
+            neg = torch.randint(0, self.num_posts, (self.B,), device=dev, generator=generator,
+                                dtype=self.edge_index.dtype)
+        else:
+            neg = _draw_link_negatives(ei[0, eid], self.num_posts, k, generator,
+                                       self.distribution, self.avoid, self.max_tries)
+            if neg.dtype != torch.int32:
+                neg = neg.to(torch.int64)
         self.blocks.arena.wait_committed()
         lib, s = N.lib(), N.stream_ptr(dev)
-        ei = self.edge_index
-        pu, pp, pn = self.pairs
-        N.check(lib.hgnn_link_seeds(N.ptr(ei[0]), N.ptr(ei[1]), N.ptr(eid), N.ptr(neg), self.B,
-                                    N.ptr(self.seeds["user"]), N.ptr(self.seeds["post"]),
-                                    N.ptr(pu), N.ptr(pp), N.ptr(pn), N.ptr(self.counts[0]), s),
-                "hgnn_link_seeds")
+        pu, pp, pn = self._pair_views
+        if not self._seeds_k:
+            N.check(lib.hgnn_link_seeds(N.ptr(ei[0]), N.ptr(ei[1]), N.ptr(eid), N.ptr(neg),
+                                        self.B, N.ptr(self.seeds["user"]),
+                                        N.ptr(self.seeds["post"]), N.ptr(pu), N.ptr(pp),
+                                        N.ptr(pn), N.ptr(self.counts[0]), s),
+                    "hgnn_link_seeds")
+        else:
+            i32 = neg.dtype == torch.int32
+            N.check(lib.hgnn_link_seeds_k(N.ptr(ei[0]), N.ptr(ei[1]), N.ptr(eid),
+                                          None if i32 else N.ptr(neg),
+                                          N.ptr(neg) if i32 else None, self.B, k,
+                                          N.ptr(self.seeds["user"]), N.ptr(self.seeds["post"]),
+                                          N.ptr(pu), N.ptr(pp), N.ptr(pn),
+                                          N.ptr(self.counts[0]), s), "hgnn_link_seeds_k")
         for h, hop in enumerate(self._hops):
             hop_seed = (int(seed) * 1_000_003 + h) & 0xFFFFFFFFFFFFFFFF   # NeighborSampler's
             N.check(lib.hgnn_sample_hop_static(*hop["args"], hop["fanout"], hop_seed,
@@ -826,7 +1057,13 @@ class LinkSampler:
             if "relabel" in hop:
                 N.check(lib.hgnn_relabel_static(*hop["relabel"], s), "hgnn_relabel_static")
         self.blocks._stage_derived(lib, s)
-        self.loss.prepare(pu, pp, pn)
+        if self._loss_default:
+            self.loss.prepare(pu, pp, pn)
+            return
+        self.loss.prepare(pu, pp, pn if k == 1 else pn.view(self.B, k),
+                          self.pos_weights[eid] if self.pos_weights is not None else None,
+                          self.seeds["post"] if self.loss.logq is not None else None,
+                          seeds_count=self.counts[0][1:2])
 
     def edge_count(self) -> torch.Tensor:
         """The staged batch's sampled message edges (every hop and relation), on the device."""
