@@ -1053,6 +1053,53 @@ int hgnn_topk_finish(const float* topv, const int32_t* topi, int64_t n_rows, int
                      const int32_t* true_cand, const int32_t* true_count, double* recall,
                      double* ndcg, int32_t* tie_flag, hgnn_stream_t stream);
 
+/* ---- Hard (model-scored) negatives: the n_neg top-scored of n_cand candidates per edge ---------
+ * hgnn_hard_negatives: for every positive edge, in the user-grouped order of rowptr_u / col_u
+ * (the arrays hgnn_edge_score_fwd_k takes), score its n_cand = M candidate posts against the
+ * edge's user and write the n_neg = k best as int32 out[E, k].  One wave per user, U[u] in
+ * registers, the M post rows streamed per edge as the scoring pass streams them; nothing but ids
+ * is written, and no gradient is involved.
+ *
+ * Candidates: cand32, int32 row-major [E, M] (candidate j of position p is element p * M + j), or
+ * cand_seed, a device seed: candidate p * M + j is uniform_draw(*seed, p * M + j, n_posts),
+ * exactly what hgnn_uniform_i32 writes for that seed.  Exactly one of the two is non-null.
+ *
+ * Per position p (user u, positive post c+ = col_u[p], candidates c_0 .. c_{M-1}):
+ *   scores    s_j = the kernel's fp32 dot product <U[u], P[c_j]> (bf16 rows widened to fp32);
+ *             a NaN score counts as -inf.
+ *   eligible  column j with 0 <= c_j < n_posts, c_j != c+, and c_j not already picked for p.
+ *             An out-of-range id is counted once in err and its row is never loaded (the load is
+ *             clamped to row 0).
+ *   picks     pick r = 0 .. k-1 is the eligible, not yet taken column of the greatest score, the
+ *             lowest column on equal scores; out[p, r] is its post id.  So a row of out is in
+ *             descending score order and holds distinct posts.
+ *   short     with no eligible column left, the pick is the lowest untaken in-range column,
+ *             whatever it holds; with none of those, c+.  Each such pick adds 1 to *short_count.
+ *             Every value written is therefore a valid post id.
+ * The result is deterministic; the two counters are the only atomics.  err (int32, nullable) is
+ * zeroed by the entry, as the loss entries do; short_count (int64, nullable) is only incremented.
+ *
+ * Limits: 1 <= n_neg <= n_cand <= 64, 1 <= n_posts < 2^31 - 1.  Widths as hgnn_edge_score_fwd:
+ * fp32 rows d <= 512, bf16 rows d % 8 == 0 and d <= 512, else HGNN_E_UNSUPPORTED.  Bad sizes, a
+ * null U, P, rowptr_u, col_u or out, and both or neither candidate source are HGNN_E_ARG.  All
+ * before any launch.  Rows are indexed as (int64_t)id * d. */
+int hgnn_hard_negatives(const float* U, const float* P, int32_t d, int64_t n_users,
+                        int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
+                        const int32_t* cand32, const uint64_t* cand_seed, int32_t n_cand,
+                        int32_t n_neg, int32_t* out, int64_t* short_count, int32_t* err,
+                        hgnn_stream_t stream);
+/* ... with bf16 U and P. */
+int hgnn_hard_negatives_bf16(const uint16_t* U, const uint16_t* P, int32_t d, int64_t n_users,
+                             int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
+                             const int32_t* cand32, const uint64_t* cand_seed, int32_t n_cand,
+                             int32_t n_neg, int32_t* out, int64_t* short_count, int32_t* err,
+                             hgnn_stream_t stream);
+/* The positions of a user a wave takes per chunk at n_cand candidates (0: n_cand out of range):
+ * min(64, hgnn_hard_neg_lds_words() / (n_cand | 1)), the kernel parking a chunk's scores and ids
+ * in two per-wave LDS arrays of hgnn_hard_neg_lds_words() words at an odd per-position stride. */
+int32_t hgnn_hard_neg_chunk(int32_t n_cand);
+int32_t hgnn_hard_neg_lds_words(void);
+
 #ifdef __cplusplus
 }
 #endif

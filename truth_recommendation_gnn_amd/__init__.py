@@ -13,7 +13,7 @@ bf16 tables, and then rank the rows rounded to bf16 on bf16 MFMA.
 from .graph import HeteroData, RelationCSR, relation_csr, CSR_CACHE  # noqa: F401
 from .nn import SAGEConv, WeightedRGCN, WeightedRGCNAuthor, HeteroSAGE  # noqa: F401
 from . import ops, synth  # noqa: F401
-from .ops import PostDistribution, SkewedNegatives  # noqa: F401
+from .ops import PostDistribution, SkewedNegatives, mine_hard_negatives  # noqa: F401
 from .metrics import SeenIndex, evaluate, recommend  # noqa: F401
 
 __version__ = "0.1.0"

@@ -208,7 +208,13 @@ _SIGS = {
                                                _c_i64, _p, ctypes.c_float, _p, _p, _p, _c_i64,
                                                _c_i64, _c_i32, _p, _p, _p, _p, _c_i64, _p, _p,
                                                _p]),
-    "hgnn_scale_unless_one": (_c_i32, [_p, _c_i64, _p, _p]),
+    "hgnn_hard_negatives": (_c_i32, [_p, _p, _c_i32, _c_i64, _c_i64, _p, _p, _p, _p, _c_i32,
+                                     _c_i32, _p, _p, _p, _p]),
+    "hgnn_hard_negatives_bf16": (_c_i32, [_p, _p, _c_i32, _c_i64, _c_i64, _p, _p, _p, _p, _c_i32,
+                                          _c_i32, _p, _p, _p, _p]),
+    "hgnn_hard_neg_chunk": (_c_i32, [_c_i32]),
+    "hgnn_hard_neg_lds_words": (_c_i32, []),
+    "hgnn_scale_unless_one":(_c_i32, [_p, _c_i64, _p, _p]),
     "hgnn_linear_fwd_f32": (_c_i32, [_p, _c_i64, _c_i32, _p, _c_i32, _p, _p, _p]),
     "hgnn_linear_dgrad_f32": (_c_i32, [_p, _c_i64, _c_i32, _p, _c_i32, _p, _p]),
     "hgnn_linear_wgrad_f32": (_c_i32, [_p, _p, _c_i64, _c_i32, _c_i32, _p, _p, _p, _c_sz, _p]),

@@ -207,6 +207,29 @@ __device__ __forceinline__ float slot_sum(float s) {
   return s;
 }
 
+// <a, b> over a slot's LPR lanes, each holding VPL fragments of W columns (the link loss's scoring
+// kernels, scoring.hip, and the hard-negative miner, hardneg.hip)
+template <int LPR, int VPL, int W>
+__device__ __forceinline__ float slot_dot(const typename Vec<W>::T (&a)[VPL],
+                                          const typename Vec<W>::T (&b)[VPL]) {
+  float s = 0.f;
+#pragma unroll
+  for (int q = 0; q < VPL; ++q) {
+    if constexpr (W == 8) {
+      s = fmaf(a[q].lo.x, b[q].lo.x, s); s = fmaf(a[q].lo.y, b[q].lo.y, s);
+      s = fmaf(a[q].lo.z, b[q].lo.z, s); s = fmaf(a[q].lo.w, b[q].lo.w, s);
+      s = fmaf(a[q].hi.x, b[q].hi.x, s); s = fmaf(a[q].hi.y, b[q].hi.y, s);
+      s = fmaf(a[q].hi.z, b[q].hi.z, s); s = fmaf(a[q].hi.w, b[q].hi.w, s);
+    } else if constexpr (W == 4) {
+      s = fmaf(a[q].x, b[q].x, s); s = fmaf(a[q].y, b[q].y, s);
+      s = fmaf(a[q].z, b[q].z, s); s = fmaf(a[q].w, b[q].w, s);
+    } else {
+      s = fmaf(a[q], b[q], s);
+    }
+  }
+  return slot_sum<LPR>(s);
+}
+
 // Hardware transcendentals (v_exp_f32 / v_log_f32 / v_rcp_f32, ~1-2 ulp).  t = exp(-|x|) in
 // (0, 1] serves both:  sigmoid(x) = x >= 0 ? 1/(1+t) : t/(1+t),  softplus(x) = max(x,0) + log(1+t)
 __device__ __forceinline__ float exp_neg_abs(float x) { return __expf(-fabsf(x)); }

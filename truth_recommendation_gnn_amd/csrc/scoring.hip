@@ -56,27 +56,6 @@ struct ScoreArgs {
   const float* edge_w;         // EW: weight of the positive edge per position (user-grouped order)
 };
 
-template <int LPR, int VPL, int W>
-__device__ __forceinline__ float slot_dot(const typename Vec<W>::T (&a)[VPL],
-                                          const typename Vec<W>::T (&b)[VPL]) {
-  float s = 0.f;
-#pragma unroll
-  for (int q = 0; q < VPL; ++q) {
-    if constexpr (W == 8) {
-      s = fmaf(a[q].lo.x, b[q].lo.x, s); s = fmaf(a[q].lo.y, b[q].lo.y, s);
-      s = fmaf(a[q].lo.z, b[q].lo.z, s); s = fmaf(a[q].lo.w, b[q].lo.w, s);
-      s = fmaf(a[q].hi.x, b[q].hi.x, s); s = fmaf(a[q].hi.y, b[q].hi.y, s);
-      s = fmaf(a[q].hi.z, b[q].hi.z, s); s = fmaf(a[q].hi.w, b[q].hi.w, s);
-    } else if constexpr (W == 4) {
-      s = fmaf(a[q].x, b[q].x, s); s = fmaf(a[q].y, b[q].y, s);
-      s = fmaf(a[q].z, b[q].z, s); s = fmaf(a[q].w, b[q].w, s);
-    } else {
-      s = fmaf(a[q], b[q], s);
-    }
-  }
-  return slot_sum<LPR>(s);
-}
-
 // XT: the element type of U and P (RowSrc).  bf16 rows are read 16 B per lane (W = 8), held packed
 // in the ping-pong sets and widened to fp32 where a step is scored; dU and the loss stay fp32.
 // EW: per-edge positive weights.  The lane that loads col[base + lane] loads edge_w[base + lane]

@@ -2691,6 +2691,117 @@ def _sample_skewed(pos_edges, num_posts: int, generator, num_neg: int, distribut
     return SkewedNegatives(out)
 
 
+HARD_NEG_MAX_CANDIDATES = 64   # the selection keeps a position's taken columns in one 64-bit mask
+
+
+def mine_hard_negatives(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: torch.Tensor,
+                        candidates, num_neg: int = 1, *, row_dtype: str = "fp32",
+                        short: Optional[torch.Tensor] = None,
+                        check: bool = False) -> SkewedNegatives:
+    """Hard (model-scored) negatives: of M candidate posts per positive edge, the ``num_neg`` = k
+    that the current tables score highest against the edge's user (``hgnn_hard_negatives``: one
+    wave per user, the M post rows streamed per edge, nothing but ids written — no ``[E, M, d]``
+    gather exists anywhere).
+
+    ``user_emb`` / ``post_emb``: the current tables, detached: no gradient flows, the result is
+    ids.  ``row_dtype="bf16"`` scores ``rows_to_bf16`` copies (``d % 8 == 0``);
+    ``torch.bfloat16`` tables may be given directly.  The default is "fp32" whatever
+    ``HGNN_ROW_DTYPE`` says, as in ``evaluate``.
+
+    ``candidates``: an int32 ``[E, M]`` (or ``[E]``) tensor in the user-grouped order of the cached
+    ``relation_csr`` (what :func:`sample_negatives` draws), a :class:`SkewedNegatives` holding
+    one, or a :class:`NegativeDraw` with ``num_neg=M`` (the pool is then drawn inside the kernel,
+    the same values as its ``tensor()``).  ``1 <= k <= M <= 64``.
+
+    Per position: pick r is the candidate of the greatest fp32 score that is in range, is not
+    the position's own positive and is not a post picked before, the lowest column on equal
+    scores (NaN counts as -inf); so a row holds distinct posts in descending score order.  Where
+    no such candidate is left the pick is the lowest unpicked in-range column whatever it holds,
+    else the positive itself, and ``short`` (an optional one-element int64 device tensor) is
+    incremented on the device, like ``kept_seen``.  ``check=True`` reads back the count of
+    out-of-range candidate ids and raises on any: the only host sync.  Deterministic.
+
+    The result is a :class:`SkewedNegatives` (int32 ``[E]`` for k = 1, else ``[E, k]``), which
+    :func:`edge_bce_loss` (``neg_order="user"``), :func:`edge_bce_loss_raw` and
+    :func:`presort_negatives` take and route to the planned dP gather.  It depends on the edges
+    and the tables' shapes only, so it may be reused over several steps.  Once mined the
+    negatives no longer follow the distribution they were drawn from: a ``logq=`` table from
+    ``dist.log_q`` does not correct for them."""
+    who = "mine_hard_negatives"
+    k = _num_neg_value(num_neg)
+    if user_emb.dim() != 2 or post_emb.dim() != 2 or user_emb.shape[1] != post_emb.shape[1]:
+        raise ValueError(f"{who}: user_emb {tuple(user_emb.shape)} and post_emb "
+                         f"{tuple(post_emb.shape)} must be [n, d] tables of one width")
+    nu, np_, d = int(user_emb.shape[0]), int(post_emb.shape[0]), int(user_emb.shape[1])
+    E = int(pos_edges.shape[1])
+    draw, cand = None, None
+    if isinstance(candidates, NegativeDraw):
+        draw = candidates
+        M, rows = draw.num_neg, draw.n // draw.num_neg
+        if draw.num_posts != np_:
+            raise ValueError(f"{who}: candidates were drawn over {draw.num_posts} posts, post_emb "
+                             f"has {np_}")
+    else:
+        cand = candidates.values if isinstance(candidates, SkewedNegatives) else candidates
+        if not isinstance(cand, torch.Tensor) or cand.dtype != torch.int32 or \
+                cand.dim() not in (1, 2):
+            got = f"{cand.dtype} {tuple(cand.shape)}" if isinstance(cand, torch.Tensor) \
+                else type(cand).__name__
+            raise ValueError(f"{who}: candidates must be int32 [E, M] (or [E]) in the "
+                             f"user-grouped order, got {got}; draw them with sample_negatives, or "
+                             "reorder COO-ordered ids with negatives_in_user_order and cast them")
+        M, rows = (1 if cand.dim() == 1 else int(cand.shape[1])), int(cand.shape[0])
+    if rows != E:
+        raise ValueError(f"{who}: candidates has {rows} rows for {E} positive edges")
+    if M < 1 or M > HARD_NEG_MAX_CANDIDATES:
+        raise ValueError(f"{who}: candidates holds M={M} per edge; 1 <= M <= "
+                         f"{HARD_NEG_MAX_CANDIDATES}")
+    if k > M:
+        raise ValueError(f"{who}: num_neg={k} exceeds the M={M} candidates per edge")
+    _draw_count(E, k)
+    bf16 = user_emb.dtype == torch.bfloat16
+    if bf16 != (post_emb.dtype == torch.bfloat16):
+        raise ValueError(f"{who}: user_emb and post_emb must both be fp32 or both bfloat16")
+    cast = _row_dtype_value(row_dtype, "row_dtype") == "bf16" and not bf16
+    if (bf16 or cast) and d % 8:
+        raise ValueError(f"{who}: row_dtype='bf16' needs d % 8 == 0, got d={d}")
+    if d > 512:
+        raise ValueError(f"{who}: d={d}; rows of at most 512 columns")
+    if short is not None and (not isinstance(short, torch.Tensor) or short.dtype != torch.int64
+                              or short.numel() != 1):
+        raise ValueError(f"{who}: short is a one-element int64 tensor")
+    dev = N.require_device(user_emb, post_emb, pos_edges, cand,
+                           draw.seed if draw is not None else None, short)
+    U, P = user_emb.detach(), post_emb.detach()
+    if cast:
+        U, P = rows_to_bf16(_check_f32(U, f"{who} user_emb")), \
+            rows_to_bf16(_check_f32(P, f"{who} post_emb"))
+    else:
+        U, P = _check_table(U, f"{who} user_emb"), _check_table(P, f"{who} post_emb")
+    out = torch.empty(E if k == 1 else (E, k), dtype=torch.int32, device=dev)
+    if E == 0:
+        return SkewedNegatives(out)
+    if np_ < 1 or np_ >= 2**31 - 1:
+        raise ValueError(f"{who}: post_emb has {np_} rows, out of range")
+    ub = relation_csr_for_loss(pos_edges, nu, np_).bwd
+    if cand is not None:
+        cand = cand.contiguous()
+    err = torch.empty(1, dtype=torch.int32, device=dev) if check else None
+    entry = "hgnn_hard_negatives_bf16" if U.dtype == torch.bfloat16 else "hgnn_hard_negatives"
+    # per position M candidate rows, M ids in (none when they are drawn here), its positive's id
+    # and k ids out; per user its own row
+    rb = _row_bytes(U)
+    nbytes = E * (M * rb + (4 * M if cand is not None else 0) + 4 + 4 * k) + nu * rb
+    with _timed("hard_negatives", nbytes):
+        N.check(getattr(N.lib(), entry)(
+            N.ptr(U), N.ptr(P), d, nu, np_, N.ptr(ub.rowptr), N.ptr(ub.col), N.ptr(cand),
+            N.ptr(draw.seed if draw is not None else None), M, k, N.ptr(out), N.ptr(short),
+            N.ptr(err), N.stream_ptr(dev)), entry)
+    if check and int(err[0]):
+        raise ValueError(f"{who}: candidate post id out of range")
+    return SkewedNegatives(out)
+
+
 # ----------------------------------------------------------------------------- composable ops
 # Differentiable single-kernel ops, used where a fused layer does not apply (the partitioned
 # multi-GPU path in parallel.py composes them around RCCL collectives).
