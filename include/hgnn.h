@@ -1100,6 +1100,73 @@ int hgnn_hard_negatives_bf16(const uint16_t* U, const uint16_t* P, int32_t d, in
 int32_t hgnn_hard_neg_chunk(int32_t n_cand);
 int32_t hgnn_hard_neg_lds_words(void);
 
+/* ---- sampled-softmax (InfoNCE) link loss (opt-in: edge_softmax_loss) -----------------------------
+ * One (1 + k)-way classification per positive edge e = (u, p_0) with negatives p_1 .. p_k:
+ *   z_j = <U[u], P[p_j]> / temperature - b[p_j]          (b = post_bias, NULL: 0)
+ *   loss = sum_e g_e (logsumexp_j z_j - z_0),    g_e = *cscale / n_edges * (edge_w ? edge_w[e] : 1)
+ * with pi_j = exp(z_j - lse_e) the coefficients of the gradient are
+ *   positive  -g_e (sum_{j >= 1} pi_j) / temperature   (= g_e (pi_0 - 1) / temperature, formed
+ *                                                        without the cancellation)
+ *   negative j g_e pi_j / temperature
+ * and dU[u] = sum coefficient x P row, dP[p] = sum coefficient x U row.  A coefficient depends on
+ * all 1 + k logits of its edge, so it is produced once, by the scoring pass, and carried to the dP
+ * gather (hgnn_coef_gather2_planned) instead of being recomputed there.
+ *
+ * hgnn_edge_softmax_fwd: one wave per user (U[u] in registers) walks each of its edges' 1 + k post
+ * rows once with an online softmax (running maximum, rescaled sums: nothing is exponentiated
+ * unshifted) and writes
+ *   dU        [n_users, d] fp32, every row once, no atomics
+ *   loss      the scalar above (deterministic reduction through part, hgnn_softmax_parts floats)
+ *   coef_neg  [n_edges, n_neg] fp32 in the user-grouped order of the negatives (an out-of-range
+ *             negative: 0)
+ *   coef_pos  [n_edges] fp32; position p of rowptr_u / col_u writes coef_pos[slot_of[p]], or
+ *             coef_pos[p] with slot_of == NULL (slot_of: int32 [n_edges], the position's index in
+ *             the post-grouped order the dP gather reads)
+ *   err       (nullable) zeroed, then the count of out-of-range negatives; such a negative takes no
+ *             part in its edge's softmax (logit -inf), reads post 0 and post_bias of nothing.
+ * rows: HGNN_ROWS_F32 or HGNN_ROWS_BF16, the format of U and P (post_bias, edge_w stay fp32).  The
+ * negatives are row-major [n_edges, n_neg] in the user-grouped order, int64 or int32 (exactly one
+ * non-null).  n_edges is the number of positive edges (no n_neg scaling convention here).
+ * HGNN_E_ARG: rows out of range, d <= 0 or a negative size, n_neg outside 1 .. 63, temperature
+ * not finite or <= 0, n_edges * n_neg >= 2^31 - 1, a null pointer, both or neither form of the
+ * negatives.  HGNN_E_UNSUPPORTED: fp32 d > 512, bf16 d % 8 != 0 or d > 512.  All before any
+ * launch.  Two runs are bitwise equal. */
+int hgnn_edge_softmax_fwd(int32_t rows, const void* U, const void* P, int32_t d, int64_t n_users,
+                          int64_t n_posts, const int32_t* rowptr_u, const int32_t* col_u,
+                          const float* edge_w, const int64_t* neg_i64, const int32_t* neg_i32,
+                          int32_t n_neg, int64_t n_edges, const float* cscale,
+                          const float* post_bias, float temperature, const int32_t* slot_of,
+                          float* dU, float* coef_pos, float* coef_neg, float* part, float* loss,
+                          int32_t* err, hgnn_stream_t stream);
+/* The positions of a user a wave takes per chunk at n_neg negatives (0: n_neg out of range):
+ * min(64, 640 / ((n_neg + 1) | 1)), the kernel parking a chunk's ids and logits in per-wave LDS at
+ * [position][column] with an odd stride, as hgnn_hard_negatives does. */
+int32_t hgnn_softmax_chunk(int32_t n_neg);
+/* floats of hgnn_edge_softmax_fwd's `part` scratch for n_users users */
+int64_t hgnn_softmax_parts(int64_t n_users);
+
+/* dP of the softmax loss: out[r] = sum_{p in [rowptr[r], rowptr[r+1])} coef_pos[p] x[col[p]]
+ *                                + sum_{q in [rowptr_n[r], rowptr_n[r+1])} coef_neg[q] x[col_n[q]]
+ * hgnn_score_gather2_planned's two lists per output row, its chunk / slab / fix-up plan for both
+ * (the positives' static plan; the negatives' made by hgnn_plan_device from rowptr_n with the same
+ * chunk, neg_slab holding 2 * neg_max_heavy rows of d floats) and its three formats of x (rows:
+ * HGNN_ROWS_*), with each pair's weight read at its position in its list instead of recomputed:
+ * coef_neg is the scoring pass's coef_neg carried through the negatives' sort as its second
+ * payload.  No rowvec, no cscale, no offsets: it reads no P rows.  Written: out (every row once),
+ * the two slabs.  Sums run in the lists' stable order; two runs are bitwise equal.
+ * HGNN_E_ARG: rows out of range, d <= 0 or another bad size, a null rowptr / rowptr_n / out, a
+ * plan without its arrays.  HGNN_E_UNSUPPORTED: a width the format does not take (bf16: d % 8 == 0
+ * and d <= 1024; zero-packed: 64 or 128; fp32: d <= 1024).  All before any launch. */
+int hgnn_coef_gather2_planned(int32_t rows, const void* x, int64_t n_x, int32_t d,
+                              const int32_t* rowptr, const int32_t* col, const float* coef_pos,
+                              const int32_t* rowptr_n, const int32_t* col_n,
+                              const float* coef_neg, int64_t n_rows, const int32_t* heavy_rows,
+                              const int32_t* heavy_first, int64_t n_heavy, int64_t n_chunks,
+                              int32_t chunk, float* slab, const int32_t* neg_heavy_rows,
+                              const int32_t* neg_heavy_first, const int32_t* d_neg_counts2,
+                              int64_t neg_max_heavy, float* neg_slab, float* out,
+                              hgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

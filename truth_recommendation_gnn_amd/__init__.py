@@ -14,6 +14,8 @@ from .graph import HeteroData, RelationCSR, relation_csr, CSR_CACHE  # noqa: F40
 from .nn import SAGEConv, WeightedRGCN, WeightedRGCNAuthor, HeteroSAGE  # noqa: F401
 from . import ops, synth  # noqa: F401
 from .ops import PostDistribution, SkewedNegatives, mine_hard_negatives  # noqa: F401
+from .ops import (edge_bce_loss, edge_softmax_loss, edge_softmax_loss_raw,  # noqa: F401
+                  link_softmax_loss)
 from .metrics import SeenIndex, evaluate, recommend  # noqa: F401
 
 __version__ = "0.1.0"

@@ -214,6 +214,14 @@ _SIGS = {
                                           _c_i32, _p, _p, _p, _p]),
     "hgnn_hard_neg_chunk": (_c_i32, [_c_i32]),
     "hgnn_hard_neg_lds_words": (_c_i32, []),
+    "hgnn_edge_softmax_fwd": (_c_i32, [_c_i32, _p, _p, _c_i32, _c_i64, _c_i64, _p, _p, _p, _p, _p,
+                                       _c_i32, _c_i64, _p, _p, ctypes.c_float, _p, _p, _p, _p, _p,
+                                       _p, _p, _p]),
+    "hgnn_softmax_chunk": (_c_i32, [_c_i32]),
+    "hgnn_softmax_parts": (_c_i64, [_c_i64]),
+    "hgnn_coef_gather2_planned": (_c_i32, [_c_i32, _p, _c_i64, _c_i32, _p, _p, _p, _p, _p, _p,
+                                           _c_i64, _p, _p, _c_i64, _c_i64, _c_i32, _p, _p, _p, _p,
+                                           _c_i64, _p, _p, _p]),
     "hgnn_scale_unless_one":(_c_i32, [_p, _c_i64, _p, _p]),
     "hgnn_linear_fwd_f32": (_c_i32, [_p, _c_i64, _c_i32, _p, _c_i32, _p, _p, _p]),
     "hgnn_linear_dgrad_f32": (_c_i32, [_p, _c_i64, _c_i32, _p, _c_i32, _p, _p]),

@@ -15,6 +15,7 @@ gradient sums the reference's autograd would do with separate add kernels happen
 from __future__ import annotations
 
 import dataclasses
+import math
 import os
 import weakref
 from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
@@ -2404,6 +2405,301 @@ def _negatives_user_order(csr, neg_p, neg_order):
 def relation_csr_for_loss(pos_edges, n_users, n_posts) -> RelationCSR:
     from .graph import relation_csr
     return relation_csr(pos_edges, n_users, n_posts)
+
+
+# ------------------------------------------------------------------ sampled-softmax link loss
+SOFTMAX_MAX_NEG = 63   # 1 + k logits of an edge fit a 64-column row of the kernel's LDS arrays
+
+
+def _temperature_value(t, who: str) -> float:
+    """``temperature`` checked before anything touches the device: a finite Python float > 0."""
+    if isinstance(t, bool) or not isinstance(t, (int, float)) or not math.isfinite(t) or t <= 0:
+        raise ValueError(f"{who}: temperature={t!r}; expected a finite Python float > 0 (a "
+                         "learned temperature is not part of this loss)")
+    return float(t)
+
+
+def _softmax_neg_count(neg_p, E: int, who: str) -> int:
+    k = _neg_count(neg_p, E, who)
+    if k > SOFTMAX_MAX_NEG:
+        raise ValueError(f"{who}: neg_p holds {k} negatives per positive edge; expected "
+                         f"1 <= k <= {SOFTMAX_MAX_NEG}")
+    return k
+
+
+def link_softmax_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: torch.Tensor,
+                      neg_p: torch.Tensor, pos_weights: Optional[torch.Tensor],
+                      weighting: str = "mean", logq: Optional[torch.Tensor] = None,
+                      temperature: float = 1.0) -> torch.Tensor:
+    """The sampled-softmax (InfoNCE) link loss with torch ops: one (1 + k)-way classification
+    per positive edge e = (u, p_0) against its negatives p_1 .. p_k (``neg_p`` of shape ``[E]`` or
+    ``[E, k]``, row e those of ``pos_edges[:, e]``),
+
+        z_j = <U[u], P[p_j]> / temperature - logq[p_j],    l_e = logsumexp_j(z_0 .. z_k) - z_0.
+
+    ``weighting="mean"``: ``mean(pos_weights) * mean_e l_e``; ``"edge"``: ``mean_e(w_e * l_e)`` —
+    the weight scales the whole edge term, there is no separate negatives' term.  ``logq``
+    (floating ``[num_posts]``, e.g. :meth:`PostDistribution.log_q`): a constant, no gradient flows
+    into it.  A negative id out of range takes no part in its edge's softmax; a negative equal to
+    the edge's own positive is not masked.  :func:`edge_softmax_loss` is the fused HIP version."""
+    _weighting_value(weighting, "link_softmax_loss")
+    tau = _temperature_value(temperature, "link_softmax_loss")
+    if isinstance(neg_p, SkewedNegatives):
+        raise TypeError("link_softmax_loss: pass SkewedNegatives.values, in the order of pos_edges")
+    _softmax_neg_count(neg_p, int(pos_edges.shape[1]), "link_softmax_loss")
+    n_posts = int(post_emb.shape[0])
+    if logq is not None:
+        _logq_rules(logq, n_posts, "link_softmax_loss")
+    pos_u, pos_p = pos_edges[0].long(), pos_edges[1].long()
+    ids = torch.cat([pos_p[:, None], neg_p.reshape(pos_p.numel(), -1).long()], dim=1)
+    valid = (ids >= 0) & (ids < n_posts)
+    ids = torch.where(valid, ids, torch.zeros_like(ids))
+    z = (user_emb[pos_u][:, None, :] * post_emb[ids]).sum(dim=-1) / tau
+    if logq is not None:
+        z = z - logq.detach().to(z.dtype)[ids]
+    z = z.masked_fill(~valid, float("-inf"))
+    term = torch.logsumexp(z, dim=1) - z[:, 0]
+    if weighting == "edge":
+        return (pos_weights * term).mean()
+    c = 1.0 if pos_weights is None else pos_weights.to(term.dtype).mean()
+    return c * term.mean()
+
+
+def _softmax_slot_of(csr: RelationCSR) -> torch.Tensor:
+    """Static per graph: the post-grouped position of each user-grouped position (int32 ``[E]``),
+    where the scoring pass puts the positives' coefficients for the dP gather to read in its own
+    order.  From the two groupings' ``perm`` (None: the identity, as in
+    :func:`edge_weights_in_kernel_order`); kept on the ``RelationCSR``."""
+    m = getattr(csr, "_slot_of", None)
+    if m is None:
+        fp, bp = csr.fwd.perm, csr.bwd.perm
+        E, dev = csr.num_edges, csr.fwd.rowptr.device
+        ident = torch.arange(E, dtype=torch.int32, device=dev)
+        if fp is None:
+            inv = ident
+        else:
+            inv = torch.empty(E, dtype=torch.int32, device=dev)
+            inv[fp.long()] = ident
+        m = (inv if bp is None else inv[bp.long()]).contiguous()
+        csr._slot_of = m
+    return m
+
+
+def _edge_softmax(U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, edge_w, logq,
+                  tau: float):
+    """Loss value and its gradients for a unit upstream gradient: ``(loss, dU, dP)``.
+
+    Three steps, in this order (the BCE path's reverse order served the sharded step's overlap,
+    which this path does not have): the scoring pass ``hgnn_edge_softmax_fwd`` (loss, dU and
+    every pair's coefficient); the negatives' (post, user) pairs sorted by post with the
+    coefficient's bits as the sort's second payload; ``hgnn_plan_device`` over the sorted lists
+    and ``hgnn_coef_gather2_planned``, which reads each pair's weight instead of recomputing it.
+    The lists are planned every step for every form of negatives.
+
+    ``U`` / ``P``: fp32 tables or both their bf16 copies.  ``neg_u_order``: the negatives in the
+    user-grouped order, ``[E]`` / ``[E, k]``.  A ``NegativeDraw`` is materialised once with the
+    uniform-draw kernel (``hgnn_uniform_i32``) and sorted as int32: ``hgnn_draw_sort_negatives``
+    has no second payload slot for the coefficient."""
+    U, P, relu_out = _loss_tables(U, P, csr, False)
+    dev = N.require_device(U, P, logq)
+    lib, s = N.lib(), N.stream_ptr(dev)
+    nu, np_, d, E = U.shape[0], P.shape[0], int(U.shape[1]), csr.num_edges
+    if E == 0:
+        return (torch.zeros((), dtype=torch.float32, device=dev),
+                torch.zeros(U.shape, dtype=torch.float32, device=dev),
+                torch.zeros(P.shape, dtype=torch.float32, device=dev))
+    k = _softmax_neg_count(neg_u_order, E, "edge_softmax_loss")
+    n = E * k
+    i64 = i32 = None
+    if isinstance(neg_u_order, NegativeDraw):
+        if neg_u_order.num_posts != np_:
+            raise ValueError("edge_softmax_loss: the NegativeDraw does not match the positive "
+                             "edges")
+        i32 = neg_u_order.tensor()
+    elif isinstance(neg_u_order, SkewedNegatives):
+        i32 = neg_u_order.values.contiguous()
+    elif neg_u_order.dtype == torch.int32:
+        i32 = neg_u_order.contiguous()
+    else:
+        i64 = neg_u_order.to(torch.int64).contiguous()
+    N.require_device(U, i32, i64)
+    # err[0]: zeroed and counted by the scoring pass, err[1] by the int64 negatives sort
+    err = torch.empty(2, dtype=torch.int32, device=dev)
+    c = cscale.to(torch.float32).reshape(()).contiguous()
+    bf16 = U.dtype == torch.bfloat16
+    ub, pf = csr.bwd, csr.fwd
+    # ---- scoring pass: BCE's bytes, 4 B out per scored pair and the 4-B index of the positives'
+    dU = torch.empty(U.shape, dtype=torch.float32, device=dev)
+    coef_pos = torch.empty(E, dtype=torch.float32, device=dev)
+    coef_neg = torch.empty(n, dtype=torch.float32, device=dev)
+    part = torch.empty(int(lib.hgnn_softmax_parts(nu)), dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    rb = _row_bytes(U)
+    ib = 4 if i32 is not None else 8
+    wb = (4 * E if edge_w is not None else 0) + (4 * E * (1 + k) if logq is not None else 0)
+    with _timed(f"edge_softmax_d{d}", E * ((1 + k) * rb + 4 + ib * k) + nu * (rb + 4 * d) + wb
+                + 4 * E * (1 + k) + 4 * E):
+        N.check(lib.hgnn_edge_softmax_fwd(
+            1 if bf16 else 0, N.ptr(U), N.ptr(P), d, nu, np_, N.ptr(ub.rowptr), N.ptr(ub.col),
+            N.ptr(edge_w.by_user if edge_w is not None else None), N.ptr(i64), N.ptr(i32), k, E,
+            N.ptr(c), N.ptr(logq), tau, N.ptr(_softmax_slot_of(csr)), N.ptr(dU), N.ptr(coef_pos),
+            N.ptr(coef_neg), N.ptr(part), N.ptr(loss), N.ptr(err if check else None), s),
+            "hgnn_edge_softmax_fwd")
+    # ---- the negatives by post, users and coefficients (as int32 bits) in that order, stable
+    rowptr_n = torch.empty(np_ + 1, dtype=torch.int32, device=dev)
+    nu_s = torch.empty(n, dtype=torch.int32, device=dev)
+    coef_s = torch.empty(n, dtype=torch.float32, device=dev)
+    uop = _user_of_draw(csr, k)
+    ws = N.workspace(lib.hgnn_sort_pairs_ws_bytes(n, np_), dev)
+    if i32 is not None:
+        # check=True: no validation pass over the keys (the scoring pass counted the ids out of
+        # range, and the call raises on any).  check=False: such a key must leave the lists, so
+        # the sort validates (one more pass over the keys) and drops it
+        with _timed("sort_negatives_coef", 4 * n * (3 * 4) + 4 * n + (0 if check else 8 * n)):
+            N.check(lib.hgnn_sort_pairs_i32(
+                N.ptr(i32), N.ptr(uop), N.ptr(coef_neg), n, np_, N.ptr(rowptr_n), N.ptr(nu_s),
+                N.ptr(coef_s), N.ptr(None if check else err[1:]), N.ptr(ws), ws.numel(), s),
+                "hgnn_sort_pairs_i32")
+    else:
+        with _timed("sort_negatives_coef", 4 * n * (2 + 1 + 6) + 4 * n):
+            N.check(lib.hgnn_sort_pairs_i64(
+                N.ptr(i64), N.ptr(uop), N.ptr(coef_neg), n, np_, N.ptr(rowptr_n), N.ptr(nu_s),
+                N.ptr(coef_s), N.ptr(err[1:]), N.ptr(ws), ws.numel(), s), "hgnn_sort_pairs_i64")
+    plan = _plan_negatives(rowptr_n, np_, n, pf.plan.chunk)
+    # ---- dP: E (1 + k) rows of U and 8 B (index, coefficient) per pair, no P rows
+    Uz = zpack_rows(U) if not bf16 and zpack_on(U, relu_out) else None
+    rows, table = (1, U) if bf16 else (2, Uz) if Uz is not None else (0, U)
+    dP = torch.empty(P.shape, dtype=torch.float32, device=dev)
+    neg_slab = torch.empty(max(2 * plan.max_heavy, 1) * d, dtype=torch.float32, device=dev)
+    pairs = E + n
+    nb = pairs * (rb + 8) + 8 * (np_ + 1) + 4 * np_ * d
+    with _timed(f"coef_gather_planned[{np_}<-{nu}]x{d}", nb):
+        N.check(lib.hgnn_coef_gather2_planned(
+            rows, N.ptr(table), nu, d, N.ptr(pf.rowptr), N.ptr(pf.col), N.ptr(coef_pos),
+            N.ptr(rowptr_n), N.ptr(nu_s), N.ptr(coef_s), np_, *_plan_args(pf.plan, d, dev),
+            N.ptr(plan.heavy_rows), N.ptr(plan.heavy_first), N.ptr(plan.counts), plan.max_heavy,
+            N.ptr(neg_slab), N.ptr(dP), s), "hgnn_coef_gather2_planned")
+    if check and int(err[0]):
+        raise ValueError("edge_softmax_loss: negative post id out of range")
+    return loss, dU, dP
+
+
+class _EdgeSoftmaxLoss(torch.autograd.Function):
+    """``_EdgeBCELoss``'s scheme for the softmax loss: the forward computes dL/dU and dL/dP with
+    the loss and keeps them; the first backward scales them in place by the upstream gradient
+    and hands them on; a second backward through a retained graph recomputes them from the saved
+    tables (the bf16 copies in the bf16 row mode) and the same negatives."""
+
+    @staticmethod
+    def forward(ctx, U, P, csr: RelationCSR, neg_u_order, cscale, check: bool, bf16: bool,
+                edge_w, logq, tau: float):
+        if bf16:
+            U, P = rows_to_bf16(U), rows_to_bf16(P)
+        loss, dU, dP = _edge_softmax(U, P, csr, neg_u_order, cscale, check, edge_w, logq, tau)
+        ctx.grads = (dU, dP)
+        ctx.save_for_backward(U, P)
+        ctx.args = (csr, neg_u_order, cscale, edge_w, logq, tau)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, go):
+        if ctx.grads is None:        # retained graph, second backward: recompute
+            U, P = ctx.saved_tensors
+            csr, neg_u_order, cscale, edge_w, logq, tau = ctx.args
+            _, dU, dP = _edge_softmax(U, P, csr, neg_u_order, cscale, False, edge_w, logq, tau)
+        else:
+            dU, dP = ctx.grads
+            ctx.grads = None         # handed on: autograd may accumulate into them from here
+        if not getattr(go, UNIT_GRAD, False):
+            g = go.to(torch.float32).reshape(()).contiguous()
+            lib, s = N.lib(), N.stream_ptr(dU.device)
+            for t in (dU, dP):   # in place; a no-op launch for loss.backward()'s gradient of 1
+                N.check(lib.hgnn_scale_unless_one(N.ptr(t), t.numel(), N.ptr(g), s),
+                        "hgnn_scale_unless_one")
+        return dU, dP, None, None, None, None, None, None, None, None
+
+
+def _softmax_args(who: str, user_emb, post_emb, pos_edges, neg_p, pos_weights, neg_order: str,
+                  weighting: str, logq, temperature):
+    """The argument rules of the two softmax entry points, all before anything touches the
+    device: ``(csr, negatives in the user-grouped order, cscale, EdgeWeights or None, logq table
+    or None, temperature)``."""
+    tau = _temperature_value(temperature, who)
+    E = int(pos_edges.shape[1])
+    if logq is not None:
+        _logq_rules(logq, int(post_emb.shape[0]), who)
+    per_edge = _edge_weighting(who, weighting, pos_weights, E, {})
+    _softmax_neg_count(neg_p, E, who)
+    _skewed_rules(neg_p, neg_order, who, {})
+    if neg_order not in ("edge", "user"):
+        raise ValueError(f"{who}: neg_order={neg_order!r}; expected 'edge' or 'user'")
+    csr = relation_csr_for_loss(pos_edges, user_emb.shape[0], post_emb.shape[0])
+    neg_u = _negatives_user_order(csr, neg_p, neg_order)
+    edge_w = edge_weights_in_kernel_order(csr, pos_weights) if per_edge else None
+    if per_edge:
+        cscale = edge_w.one
+    elif pos_weights is None:
+        cscale = torch.ones((), dtype=torch.float32, device=user_emb.device)
+    else:
+        cscale = pos_weights.to(torch.float32).mean()
+    table = logq_table(csr, logq) if logq is not None else None
+    return csr, neg_u, cscale, edge_w, table, tau
+
+
+def edge_softmax_loss(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: torch.Tensor,
+                      neg_p, pos_weights: Optional[torch.Tensor], neg_order: str = "edge",
+                      check: bool = True, row_dtype: Optional[str] = None,
+                      weighting: str = "mean", logq: Optional[torch.Tensor] = None,
+                      temperature: float = 1.0) -> torch.Tensor:
+    """Fused HIP version of :func:`link_softmax_loss` (same value, same gradients): the sampled
+    softmax over each positive edge and its k negatives, 1 <= k <= 63, with a temperature.
+
+    ``neg_p`` comes in every form :func:`edge_bce_loss` takes — int64 / int32 ``[E]`` or
+    ``[E, k]`` tensors, a ``NegativeDraw``, ``SkewedNegatives`` — with ``neg_order`` as there; the
+    same ids give bitwise the same results in every form.  Mined hard negatives
+    (:func:`mine_hard_negatives`) and popularity-weighted draws (:func:`sample_negatives` with
+    ``distribution`` / ``avoid``) are the expected input, so the negatives' lists per post get a
+    heavy-row plan on the device every step, whatever their form.  ``weighting``, ``logq`` and
+    ``row_dtype`` are :func:`edge_bce_loss`'s (``logq=dist.log_q(k)`` is the correction this loss
+    was invented with; with "edge" the weight scales the whole edge term); ``temperature`` is a
+    finite Python float > 0, not a tensor.  ``check=True`` raises on a negative id out of range
+    (one host sync); with ``check=False`` such a negative takes no part in its edge's softmax.
+    Accidental hits (a negative equal to the edge's positive) are not masked.
+
+    One scoring pass (``hgnn_edge_softmax_fwd``: every post row read once, an online softmax per
+    edge, dU without atomics) emits each pair's gradient coefficient, the negatives' sort carries
+    it as a payload, and ``hgnn_coef_gather2_planned`` sums dP from it (``_edge_softmax``).
+    ``HGNN_ZPACK`` applies to the gather's user rows as in :func:`edge_bce_loss`.  The sharded
+    step's arguments and ``presorted=`` are not part of this loss."""
+    who = "edge_softmax_loss"
+    bf16 = resolve_row_dtype(row_dtype) == "bf16" and user_emb.shape[1] % 8 == 0
+    csr, neg_u, cscale, edge_w, table, tau = _softmax_args(
+        who, user_emb, post_emb, pos_edges, neg_p, pos_weights, neg_order, weighting, logq,
+        temperature)
+    if bf16:
+        _check_f32(user_emb, f"{who} user_emb")
+        _check_f32(post_emb, f"{who} post_emb")
+    return _EdgeSoftmaxLoss.apply(user_emb, post_emb, csr, neg_u, cscale, check, bf16, edge_w,
+                                  table, tau)
+
+
+def edge_softmax_loss_raw(user_emb: torch.Tensor, post_emb: torch.Tensor, pos_edges: torch.Tensor,
+                          neg_p, pos_weights: Optional[torch.Tensor], neg_order: str = "edge",
+                          check: bool = True, row_dtype: str = "fp32", weighting: str = "mean",
+                          logq: Optional[torch.Tensor] = None, temperature: float = 1.0):
+    """:func:`edge_softmax_loss` outside autograd: ``(loss, dL/dU, dL/dP)`` from the same
+    kernels.  ``row_dtype`` is "fp32" unless asked otherwise (never ``ROW_DTYPE``), as
+    :func:`edge_bce_loss_raw`'s."""
+    who = "edge_softmax_loss_raw"
+    bf16 = _row_dtype_value(row_dtype, "row_dtype") == "bf16" and user_emb.shape[1] % 8 == 0
+    csr, neg_u, cscale, edge_w, table, tau = _softmax_args(
+        who, user_emb, post_emb, pos_edges, neg_p, pos_weights, neg_order, weighting, logq,
+        temperature)
+    if bf16:
+        user_emb = rows_to_bf16(_check_f32(user_emb, f"{who} user_emb"))
+        post_emb = rows_to_bf16(_check_f32(post_emb, f"{who} post_emb"))
+    return _edge_softmax(user_emb, post_emb, csr, neg_u, cscale, check, edge_w, table, tau)
 
 
 class NegativeDraw:
