@@ -701,10 +701,11 @@ int hgnn_edge_score_fwd_k_bf16(const uint16_t* U, const uint16_t* P, int32_t d, 
  *   dU[u] = sum h P[.],  dP[p] = sum h U[.],  h = scale * (sigmoid(z_pos) - 1)  or  scale * sigmoid(z_neg)
  * With b[p] = log(k Q(p)) for negatives drawn k per edge from Q this is the logQ correction of
  * sampled softmax / NCE.  The dot products, the rows read, the sums and their order are those of
- * the entries these stand beside; only the scalar fed to the sigmoid and the softplus moves, and
- * the positives' coefficient sigmoid(z) - 1 is formed as -sigmoid(-z) from the same exponential
- * (b = log(1/T) puts z near +22, where the difference is exactly 0 in fp32), so b = 0 gives their
- * results to rounding, and two runs are bitwise equal.  With bf16 rows b stays fp32.
+ * the entries these stand beside; only the scalar fed to the sigmoid and the softplus moves.  As
+ * in every entry of the loss the positives' coefficient sigmoid(z) - 1 is formed as -sigmoid(-z)
+ * from the same exponential (b = log(1/T) puts z near +22, where the difference is exactly 0 in
+ * fp32) and the softplus with a corrected log1p (csrc/bce_terms.h), so b = 0 gives their results,
+ * and two runs are bitwise equal.  With bf16 rows b stays fp32.
  *
  * hgnn_edge_score_fwd_k_lq: hgnn_edge_score_fwd_k (any n_neg >= 1, edge_w nullable) with
  * post_bias = b.  Scaling convention: hgnn_edge_score_fwd_k's, n_edges = E * n_neg and

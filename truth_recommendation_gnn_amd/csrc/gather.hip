@@ -12,6 +12,11 @@
 // No atomics: each destination row is owned by one wave, so sums are deterministic.  Rows longer
 // than `chunk` edges (power-law heads) are split by the plan into chunk-sized items whose
 // partial sums go to a slab, then k_fixup adds them in chunk order.
+//
+// Score mode (the link loss's dP): an edge's weight is its BCE coefficient, recomputed from the
+// score with bce_terms.h's helpers as the scoring pass forms it (scoring.hip): a positive's
+// sigma(s) - 1 as -sigma(-s) (pos_coef_t), a negative's sigma(s), in every instantiation -- plain,
+// weighted, zero-packed, planned, with or without the logQ offset.
 #include "hgnn_common.h"
 #include "zpack.h"
 #include "zpack_lanes.h"
@@ -48,7 +53,7 @@ struct GatherArgs {
   const void* rowvec;          // (of the source table's element type)
   const float* cscale;
   float inv_e;
-  int32_t score;               // 1: c*inv_e*(sigmoid(s)-1)   2: inv_e*sigmoid(s)
+  int32_t score;               // 1: -c*inv_e*sigmoid(-s)   2: inv_e*sigmoid(s)
   // hgnn_score_gather2: a second grouped list (the negatives, mode 2, no heavy-row plan) summed
   // into the same rows in the same pass; null otherwise
   const int32_t* rowptr2;
@@ -148,20 +153,13 @@ __device__ __forceinline__ void segment_sum_zp(const GatherArgs& a, const int32_
         float sdot = 0.f;
         sdot += V::dot(rv, v[u]);
         sdot = slot_sum<LPR>(sdot);
-        if constexpr (LQ) {   // (segment_sum's LQ weights)
-          sdot -= rb;
-          const float tt = exp_neg_abs(sdot);
-          if constexpr (EW)
-            we[u] = -cw * __shfl(widx, (j + u * NS + slot) & 63, 64) * sigmoid_t(-sdot, tt);
-          else
-            we[u] = score == 1 ? -cw * sigmoid_t(-sdot, tt) : cw * sigmoid_t(sdot, tt);
-          continue;
-        }
-        const float sg = sigmoid_t(sdot, exp_neg_abs(sdot));
-        if constexpr (EW)   // (the weighted list is the positives': mode 1)
-          we[u] = cw * __shfl(widx, (j + u * NS + slot) & 63, 64) * (sg - 1.f);
+        if constexpr (LQ) sdot -= rb;
+        // (segment_sum's weights: pos_coef_t for the positives, mode 1)
+        const float tt = exp_neg_abs(sdot);
+        if constexpr (EW)   // (the weighted list is the positives')
+          we[u] = cw * __shfl(widx, (j + u * NS + slot) & 63, 64) * pos_coef_t(sdot, tt);
         else
-          we[u] = cw * (score == 1 ? sg - 1.f : sg);
+          we[u] = cw * pair_coef_t(score == 1, sdot, tt);
       }
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) V::fma(acc, we[u], v[u]);
@@ -192,8 +190,8 @@ __device__ __forceinline__ void segment_sum_zp(const GatherArgs& a, const int32_
 // widened to fp32 where they are summed.  Everything after the load is fp32 either way.
 //
 // LQ with SC (hgnn_score_gather2_lq): the logit is the score less rb, the row's own offset
-// (row_bias[row], loaded once per item by gather_item), for either weight mode; the weights are
-// the scoring pass's LQ expressions, so both passes give an edge one coefficient.
+// (row_bias[row], loaded once per item by gather_item), for either weight mode; the weights'
+// expressions are those of the other instantiations.
 template <int LPR, int VPL, int W, int UNROLL, bool HAS_W, bool SC, bool HOT, typename XT = float,
           int ZP = 0, bool LQ = false>
 __device__ __forceinline__ void segment_sum(const GatherArgs& a, const int32_t* col, int score,
@@ -257,18 +255,12 @@ __device__ __forceinline__ void segment_sum(const GatherArgs& a, const int32_t* 
 #pragma unroll
           for (int q = 0; q < VPL; ++q) sdot += V::dot(rv[q], S::widen(v[u][q]));
           sdot = slot_sum<LPR>(sdot);
-          if constexpr (LQ) {
-            // the positives' sigmoid(z) - 1 formed as -sigmoid(-z) (the same t, no cancellation):
-            // an offset of log(1/T) puts z near +22, where 1/(1 + t) - 1 is exactly 0 in fp32
-            sdot -= rb;
-            const float tt = exp_neg_abs(sdot);
-            if constexpr (HAS_W) we[u] = -cw * we[u] * sigmoid_t(-sdot, tt);
-            else we[u] = score == 1 ? -cw * sigmoid_t(-sdot, tt) : cw * sigmoid_t(sdot, tt);
-            continue;
-          }
-          const float sg = sigmoid_t(sdot, exp_neg_abs(sdot));
-          if constexpr (HAS_W) we[u] = cw * we[u] * (sg - 1.f);   // (the positives: mode 1)
-          else we[u] = cw * (score == 1 ? sg - 1.f : sg);
+          if constexpr (LQ) sdot -= rb;
+          // the positives' sigmoid(z) - 1 formed as -sigmoid(-z) (pos_coef_t: the same t, no
+          // cancellation): from z ~ 17 up 1/(1 + t) - 1 is exactly 0 in fp32
+          const float tt = exp_neg_abs(sdot);
+          if constexpr (HAS_W) we[u] = cw * we[u] * pos_coef_t(sdot, tt);   // (mode 1)
+          else we[u] = cw * pair_coef_t(score == 1, sdot, tt);
         }
       }
 #pragma unroll

@@ -7,6 +7,7 @@
 #include <stdarg.h>
 
 #include "../../include/hgnn.h"
+#include "bce_terms.h"
 
 namespace hgnn {
 
@@ -230,13 +231,8 @@ __device__ __forceinline__ float slot_dot(const typename Vec<W>::T (&a)[VPL],
   return slot_sum<LPR>(s);
 }
 
-// Hardware transcendentals (v_exp_f32 / v_log_f32 / v_rcp_f32, ~1-2 ulp).  t = exp(-|x|) in
-// (0, 1] serves both:  sigmoid(x) = x >= 0 ? 1/(1+t) : t/(1+t),  softplus(x) = max(x,0) + log(1+t)
-__device__ __forceinline__ float exp_neg_abs(float x) { return __expf(-fabsf(x)); }
-__device__ __forceinline__ float sigmoid_t(float x, float t) {
-  const float r = __builtin_amdgcn_rcpf(1.f + t);
-  return x >= 0.f ? r : t * r;
-}
+// (The BCE link loss's terms from t = exp(-|x|) -- exp_neg_abs, sigmoid_t, pos_coef_t, softplus_t
+// -- are bce_terms.h's, included above: plain C++ that the host check compiles too.)
 
 // Uniform int32 in [0, hi) of draw i: splitmix64 of seed + i * golden ratio, then the high 32 bits
 // scaled by hi (hgnn_uniform_i32; the negatives sort regenerates the same draws in its first pass).

@@ -17,6 +17,12 @@
 //   hpos (written at the edge's post-grouped position) and (n_e, u_e, hneg) for the negatives.
 // dP is then two K1-style weighted gathers of U rows (gather.hip): positives over the post-
 // grouped CSR, negatives over the (n_e)-sorted list (hgnn_sort_pairs_i32).  Deterministic.
+//
+// Every kernel here and in gather.hip forms a pair's terms with bce_terms.h's helpers, from
+// t = exp(-|s|):  sigma(s) - 1 as -sigma(-s) = -t/(1+t) for s >= 0 (pos_coef_t; a product, so a
+// saturated positive keeps its digits where 1/(1+t) - 1 is 0 from s ~ 17), and softplus as
+// max(x, 0) + log1p(t) with the rounding of 1 + t corrected (softplus_t).  Coefficients and loss
+// terms are accurate relative to themselves down to the underflow of t (|s| ~ 87).
 #include "hgnn_common.h"
 
 // Post rows of the negatives (uniform draws, little reuse) are read with nt loads: cfg4 scoring
@@ -139,7 +145,7 @@ __global__ void __launch_bounds__(256) k_edge_score(const ScoreArgs a) {
         const float sp = slot_dot<LPR, VPL, W>(uv, vp);
         const float sn = slot_dot<LPR, VPL, W>(uv, vn);
         const float tp = exp_neg_abs(sp), tn = exp_neg_abs(sn);
-        float hp = c * a.inv_e * (sigmoid_t(sp, tp) - 1.f);
+        float hp = c * a.inv_e * pos_coef_t(sp, tp);
         float hn = a.inv_e * sigmoid_t(sn, tn);
         float we = 1.f;
         if constexpr (EW) {
@@ -147,12 +153,12 @@ __global__ void __launch_bounds__(256) k_edge_score(const ScoreArgs a) {
           hp *= we;
         }
         if (e >= n) hp = hn = 0.f;
-        // loss terms once per edge, on the slot's first lane:
-        //   softplus(-sp) = max(-sp, 0) + log(1 + t),  softplus(sn) = max(sn, 0) + log(1 + t)
+        // loss terms once per edge, on the slot's first lane: softplus(-sp) and softplus(sn), the
+        // positive's weighted by an explicit fma (k_edge_score_k forms the same bits)
         if (sl == 0 && e < n) {
-          if constexpr (EW) lpos += we * (fmaxf(-sp, 0.f) + __logf(1.f + tp));
-          else lpos += fmaxf(-sp, 0.f) + __logf(1.f + tp);
-          lneg += fmaxf(sn, 0.f) + __logf(1.f + tn);
+          if constexpr (EW) lpos = fmaf(we, softplus_t(-sp, tp), lpos);
+          else lpos += softplus_t(-sp, tp);
+          lneg += softplus_t(sn, tn);
         }
 #pragma unroll
         for (int q = 0; q < VPL; ++q) {
@@ -244,9 +250,9 @@ struct ScoreArgsK {
 // issued ahead of the sweep's first rows and is older than they are, so the first step's wait for
 // its rows covers it); an id kept as -1 reads entry 0, as its row load reads post 0.  The value
 // reaches the scoring slot by the shuffle the id takes and is subtracted from the dot product
-// before exp_neg_abs; the rows, the sums into dU and their order are unchanged.  The one other
-// difference is the positives' coefficient sigmoid(z) - 1, formed as -sigmoid(-z) (score_step).
-// Its own instantiations: with LQ off this is the code it was.
+// before exp_neg_abs; the rows, the sums into dU and their order are unchanged, and so are the
+// expressions of the coefficients and the loss terms (bce_terms.h, one spelling for every path:
+// a table of zeros gives the numbers of the call without one).  Its own instantiations.
 template <int LPR, int VPL, int W, bool NT = false, typename XT = float, bool EW = false,
           bool LQ = false>
 __global__ void __launch_bounds__(256) k_edge_score_k(const ScoreArgsK ak) {
@@ -347,13 +353,11 @@ __global__ void __launch_bounds__(256) k_edge_score_k(const ScoreArgsK ak) {
         const float t0 = exp_neg_abs(s0), t1 = exp_neg_abs(s1);
         float h0, h1 = 0.f;
         bool ok0 = e < n, ok1 = e < n;
-        if constexpr (pos0 && LQ) {
-          // sigmoid(z) - 1 formed as -sigmoid(-z) from the same t: no cancellation.  An offset of
-          // log(1/T) (a post of weight 0, PostDistribution.log_q) puts z near +22, where
-          // 1/(1 + t) - 1 is exactly 0 in fp32 and the post's positives would push nothing.
-          h0 = -(c * a.inv_e) * sigmoid_t(-s0, t0);
-        } else if constexpr (pos0) {
-          h0 = c * a.inv_e * (sigmoid_t(s0, t0) - 1.f);
+        if constexpr (pos0) {
+          // sigmoid(z) - 1 as -sigmoid(-z) (pos_coef_t): a trained model's positives, or an offset
+          // of log(1/T) (a post of weight 0, PostDistribution.log_q), sit at z of 17 and more,
+          // where 1/(1 + t) - 1 is exactly 0 in fp32 and the edge would push nothing
+          h0 = c * a.inv_e * pos_coef_t(s0, t0);
         } else {
           h0 = a.inv_e * sigmoid_t(s0, t0);
           ok0 = ok0 && __shfl(id0, e & 63, 64) >= 0;
@@ -369,31 +373,26 @@ __global__ void __launch_bounds__(256) k_edge_score_k(const ScoreArgsK ak) {
         }
         if (!ok0) h0 = 0.f;
         if (!ok1) h1 = 0.f;
-        // loss terms once per row, on the slot's first lane (k_edge_score's expressions)
-        if (sl == 0) {
-          if constexpr (pos0) {
-            if (ok0) {
-              // (a rounded product, then the add: what k_edge_score's expression compiles to,
-              // where this one would contract to an fma and differ in the loss's last bits)
-              const float sp0 = fmaxf(-s0, 0.f) + __logf(1.f + t0);
-              if constexpr (EW) {
-#pragma clang fp contract(off)
-                lpos += we * sp0;
-              } else {
-                lpos += sp0;
-              }
-            }
-          } else {
-            if (ok0) lneg += fmaxf(s0, 0.f) + __logf(1.f + t0);
-          }
-          if constexpr (two) {
-            if (ok1) lneg += fmaxf(s1, 0.f) + __logf(1.f + t1);
-          }
-        }
 #pragma unroll
         for (int q = 0; q < VPL; ++q) {
           V::fma(acc[q], h0, v0[q]);
           if constexpr (two) V::fma(acc[q], h1, v1[q]);
+        }
+        // loss terms once per row, on the slot's first lane (k_edge_score's expressions), after
+        // the rows' last use: the terms' temporaries then take the registers the rows leave
+        if (sl == 0) {
+          if constexpr (pos0) {
+            if (ok0) {
+              // (the explicit fma of k_edge_score: the same bits whatever the compiler contracts)
+              if constexpr (EW) lpos = fmaf(we, softplus_t(-s0, t0), lpos);
+              else lpos += softplus_t(-s0, t0);
+            }
+          } else {
+            if (ok0) lneg += softplus_t(s0, t0);
+          }
+          if constexpr (two) {
+            if (ok1) lneg += softplus_t(s1, t1);
+          }
         }
       };
       auto sweep = [&](auto pos0, auto two, int id0, int id1, float q0, float q1) {
